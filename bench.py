@@ -13,6 +13,11 @@ anything touches the GPU, and exits with the child's code.  It refuses (non-zero
 
 One "step" = one pass of the hot path over one batch.  Inputs are resident in HBM when the timed region starts
 (bmpc_solve_dev_async with device pointers).  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only (`value`, `ms_per_step`).  `--full` adds everything else in the same line: solver
+statistics and the roofline of the step-0 batch solved alone, the shard check of a multi-GPU run, one batch at a time, the
+figures with the transfers inside, configs[4] and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+returned (x, f, viol, iters, status of its batch) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -42,6 +47,7 @@ FP64_VEC_PEAK_TFLOPS = 78.6    # vector FP64 peak (spec); the binding resource o
 MAX_DISTINCT = 16              # distinct batches resident at once (231 MB each); longer runs (and the warm-up) cycle through them
 MAX_DISTINCT_MULTI = 8         # ... per rank of a multi-GPU run: 6 generator processes per rank build 8 batches in < 60 s
 RIC_FLOPS_PER_STAGE = 1.13e5   # Riccati share of the SURVEY 8(d) stage model (F_stage = 1.2e5: n_x = 26, n_u = 9), per instance, stage, sweep
+DUMP_BUDGET = 64_000_000       # bytes --dump-outputs may write in all
 
 
 def alg_bytes_per_solve(N):
@@ -78,6 +84,126 @@ def block_diffs(N, xa, xb):
               "p": (28 * N, 34 * N), "v": (34 * N, 40 * N), "slacks": (40 * N, 44 * N + 6)}
     d = np.abs(xa - xb)
     return {k: float(d[:, a:b].max()) if d.size else None for k, (a, b) in blocks.items()}
+
+
+def usable_cpus():
+    """CPUs this process may run on: the affinity mask, cut down by a cgroup CPU quota (a container can see every core of the
+    host while its quota allows a few)."""
+    n = len(os.sched_getaffinity(0))
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
+# ---- problem instances ----
+# scenes.make_batch draws everything for a batch from one random stream, in instance order, in the calling process, and maps
+# the per-instance construction over its pool.  Those draws take ~2.5 s per batch: with many batches they, not the
+# construction, set the generation time.  generate() therefore runs the draws of each batch in a worker too: the main process
+# only computes the kinematics the draws need (on the GPU, recorded), the worker replays them into make_batch and hands back
+# the per-instance jobs, which the pool builds.  The result is bitwise what make_batch returns for the same seed.
+
+_FK_KEYS = ("ee_pos", "ee_rot", "col_pts")      # the kinematics outputs make_batch reads
+
+
+def _fk_recorder(fk):
+    """fk wrapper that keeps the input and the outputs make_batch reads of every call, in call order."""
+    calls = []
+
+    def rec(q, dq=None):
+        r = fk(q, dq)
+        calls.append((np.array(q, dtype=float), {k: r[k] for k in _FK_KEYS}))
+        return r
+    return rec, calls
+
+
+def _fk_replayer(calls):
+    """fk stand-in that returns the recorded outputs, and fails unless it is asked for exactly the recorded inputs."""
+    it = iter(calls)
+
+    def replay(q, dq=None):
+        q0, r = next(it)
+        if not np.array_equal(np.asarray(q, dtype=float), q0):
+            raise RuntimeError("bench.py: the generator asked for other kinematics than were recorded")
+        return r
+    return replay
+
+
+class _JobCapture:
+    """Stands in for make_batch's pool: keeps the per-instance jobs instead of building them."""
+    jobs = None
+
+    def imap(self, fn, jobs, chunksize=1):
+        self.jobs = jobs
+        return iter([(0.0, 0.0, 0.0, 0.0, None)] * len(jobs))
+
+
+def _draw_jobs(B, N, seed, fk_calls):
+    """(worker) the random draws of make_batch for one batch -> its per-instance jobs."""
+    from boundplanner_amd import scenes
+    cap = _JobCapture()
+    scenes.make_batch(B, N, seed, _fk_replayer(fk_calls), randomize_sets=True, pool=cap)
+    return cap.jobs
+
+
+def _build_chunk(jobs):
+    """(worker) make_batch's per-instance construction over consecutive jobs -> x0, lbx, ubx, p stacked (one row per job)."""
+    from boundplanner_amd import scenes
+    res = [scenes._build_instance(j) for j in jobs]
+    return tuple(np.array([r[i] for r in res], dtype=float) for i in range(4))
+
+
+def generate(seeds, B, N, fk, pool=None):
+    """Yields, seed by seed, the arrays x0, lbx, ubx, p of scenes.make_batch(B, N, seed, fk, randomize_sets=True).  `pool`: a
+    fork pool of processes that never touch the GPU (None: everything in this process)."""
+    from boundplanner_amd import scenes
+    if pool is None:
+        for seed in seeds:
+            batch = scenes.make_batch(B, N, seed, fk, randomize_sets=True)
+            yield {k: batch[k] for k in ("x0", "lbx", "ubx", "p")}
+        return
+    drawn = []
+    for seed in seeds:
+        rec, calls = _fk_recorder(fk)
+        q_start, q_goal = scenes.sample_start_goal(np.random.default_rng(seed), rec, B)      # make_batch's kinematics calls, in order
+        rec(q_start); rec(q_goal)
+        drawn.append(pool.apply_async(_draw_jobs, (B, N, seed, calls)))
+    chunk = 64
+    built = []
+    for d in drawn:
+        jobs = d.get()
+        built.append(pool.imap(_build_chunk, [jobs[i:i + chunk] for i in range(0, B, chunk)]))
+    for res in built:
+        out = {}
+        for i, arrays in enumerate(res):
+            for k, a in zip(("x0", "lbx", "ubx", "p"), arrays):
+                if k not in out:
+                    out[k] = np.empty((B, a.shape[1]))
+                out[k][i * chunk:i * chunk + len(a)] = a
+        yield out
+
+
+def write_outputs(dirname, groups, budget=DUMP_BUDGET):
+    """--dump-outputs: `groups` = [(prefix, {name: array with one row per instance})]; every array goes to
+    dirname/<prefix><name>.npy as float64.  Each group may use an equal share of `budget`; a group larger than that is cut to a
+    fixed, seeded sample of its rows (the same rows for all its arrays), whose indices go to <prefix>rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // max(1, len(groups))
+    for prefix, arrays in groups:
+        arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+        n = len(next(iter(arrays.values())))
+        row_bytes = sum(a[0].nbytes for a in arrays.values())
+        if n * row_bytes > share:
+            k = share // (row_bytes + 8)
+            rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            arrays = {name: a[rows] for name, a in arrays.items()}
+            arrays["rows"] = rows.astype(np.float64)
+        for name, a in arrays.items():
+            np.save(os.path.join(dirname, f"{prefix}{name}.npy"), a)
 
 
 def visible_gpus():
@@ -145,6 +271,11 @@ def main():
     ap.add_argument("--opt", action="append", default=[], help="solver option key=value (bmpc_opts field), A/B runs")
     ap.add_argument("--same-batch", action="store_true", help="every step solves the seed-8192 batch (profiling passes)")
     ap.add_argument("--gen-workers", type=int, default=None, help="processes building problem instances (0: in this process)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: solver statistics and roofline of "
+                    "the step-0 batch solved alone, the shard check (--gpus N), one batch at a time, the transfers inside, configs[4], the "
+                    "CPU baseline (the --no-* options below switch legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write x, f, viol, iters, status of the last timed step's batch "
+                    "to DIR/<name>.npy (float64; a larger output than 64 MB in all is cut to a fixed, seeded sample of rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the single-batch, PCIe-inclusive and closed-loop measurements")
     ap.add_argument("--no-closed-loop", action="store_true", help="skip the configs[4] leg")
@@ -153,6 +284,8 @@ def main():
                     "the N-rank run; the line it prints is marked and is NOT a scaling measurement")
     ap.add_argument("--closed-loop-steps", type=int, default=200, help="MPC steps of the configs[4] leg (4096 rollouts, N=30; the config has 200)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -173,7 +306,7 @@ def main():
     n_distinct = M * ((n_distinct + M - 1) // M)
     # instance-building workers: forked BEFORE this process initialises the GPU; they never touch it
     pool = None
-    n_workers = args.gen_workers if args.gen_workers is not None else max(0, min(32, len(os.sched_getaffinity(0)) // max(1, world) - 2))
+    n_workers = args.gen_workers if args.gen_workers is not None else max(0, min(32, usable_cpus() // max(1, world) - 1))
     if n_workers > 0 and n_distinct > 1:
         import multiprocessing as mp
         pool = mp.get_context("fork").Pool(n_workers)
@@ -213,17 +346,19 @@ def main():
     t0 = time.time()
     host0 = None
     d = {k: torch.empty((n_distinct * B, be.n_p if k == "p" else n_w), dtype=torch.float64, device=dev) for k in ("x0", "lbx", "ubx", "p")}
-    for s in range(n_distinct):
-        if args.same_batch and s > 0:
-            for k in d:
-                d[k][s * B:(s + 1) * B] = d[k][:B]
-            continue
-        batch = scenes.make_batch(B, N, batch_seed(world, rank, s), be.fk, randomize_sets=True, pool=pool)
+    # fresh batches: at most MAX_DISTINCT(_MULTI) -- the ring of whole solver calls can round n_distinct up to twice that, and
+    # generation is CPU-bound (~1 s per batch on 16 cores): slots past the fresh ones repeat them
+    n_gen = 1 if args.same_batch else min(n_distinct, MAX_DISTINCT if world == 1 else MAX_DISTINCT_MULTI)
+    for s, batch in enumerate(generate([batch_seed(world, rank, s) for s in range(n_gen)], B, N, be.fk, pool)):
         hb = {k: big(batch[k]) for k in ("x0", "lbx", "ubx", "p")}
         if s == 0:
             host0 = hb
         for k in d:
             d[k][s * B:(s + 1) * B] = torch.from_numpy(hb[k]).to(dev)
+    for s in range(n_gen, n_distinct):      # slot s holds fresh batch s mod n_gen (--same-batch: the step-0 batch everywhere)
+        r = s % n_gen
+        for k in d:
+            d[k][s * B:(s + 1) * B] = d[k][r * B:(r + 1) * B]
     if pool is not None:
         pool.close(); pool.join()
     t_gen = time.time() - t0
@@ -245,7 +380,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    profiling_pass = world == 1 and depth == 1 and M == 1 and n_distinct == 1      # (the timed batch IS the lone batch below)
+    profiling_pass = args.full and world == 1 and depth == 1 and M == 1 and n_distinct == 1      # (the timed batch IS the lone batch below)
     if rank == 0 and profiling_pass:
         be.time_ric(True)
     stream.run(args.warmup)
@@ -259,6 +394,45 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step = the last batch of the last solver call (rows (m_last - 1) * B ... of its handle's outputs)
+        m_last = args.steps - M * ((args.steps - 1) // M)
+        o = outs[(stream.calls - 1) % depth]
+        last = slice((m_last - 1) * B, m_last * B)
+        groups = [("", {k: o[k][last].cpu().numpy() for k in ("x", "f", "viol", "iters", "status")})]
+        if world > 1:           # the same step's x of every rank, as the all-gather of that call delivered it
+            n = m_last * B
+            groups.append(("gathered_", {"x": torch.cat([gathered[r * n + (m_last - 1) * B:(r + 1) * n] for r in range(world)]).cpu().numpy()}))
+        write_outputs(args.dump_outputs, groups)
+
+    total_solves = world * B * args.steps
+    value = total_solves / elapsed
+    gather_name = "gloo all-gather (one-GPU rehearsal)" if args.rehearse_one_gpu else "RCCL all-gather"
+    out = {
+        "metric": "MPC solves/sec (whole node), iiwa14 7-DOF, N=20",
+        "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": (f"BASELINE configs[2]: {B}-batch, randomized convex-set obstacles, N={N}, cold start, tol 1e-5, "
+                                "max_iter 100; a fresh batch every step" if world == 1 else
+                                f"BASELINE configs[3]: one {world * B}-batch (seed 65536) cut into {world} contiguous shards of {B}, "
+                                f"randomized convex-set obstacles, N={N}, cold start, {gather_name} of x"),
+                   "value_is": "inputs resident in HBM when the timed region starts, pipelined solver calls (solver_handles_in_flight / "
+                               "batches_per_solver_call): `value` EXCLUDES host<->device transfers.  The SURVEY 8(d) figure with the transfers "
+                               "inside the same schedule is value_pcie_inclusive_pipelined; value_single_batch / value_pcie_inclusive are one batch at a time",
+                   "batch_per_gpu": B, "horizon": N, "distinct_batches": n_distinct, "fresh_batches": n_gen,
+                   "sharding": f"contiguous shards, no data-path collective, {gather_name} of x" if world > 1 else "single GPU",
+                   "hess": int(be.opts.hess), "solver_handles_in_flight": depth,
+                   "batches_per_solver_call": M, "batches_in_flight": depth * M, "pool_slots": args.pool},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     event_ms = float(np.mean(stream.kernel_ms)) if stream.kernel_ms else None
 
     # ---- untimed: the seed-of-step-0 batch alone on one handle -> solver statistics, parity sample, shard check ----
@@ -298,8 +472,6 @@ def main():
                 if not same:
                     raise SystemExit(f"bench.py: shard {r}: gathered solutions differ from a stand-alone solve")
 
-    total_solves = world * B * args.steps
-    value = total_solves / elapsed
     # GPU time per batch: with several calls in flight they overlap, so the per-batch share of the timed region is the
     # honest denominator (event_ms_per_batch = HIP events around one call on its own stream / its batches)
     k_ms = event_ms if depth == 1 else 1e3 * elapsed / args.steps
@@ -355,23 +527,7 @@ def main():
                  "hbm_alg_gbs": ach_gbs, "hbm_alg_frac": ach_gbs / HBM_PEAK_GBS, "alg_bytes_per_solve": alg_bytes_per_solve(N),
                  "per_batch_ms": k_ms, "event_ms_per_batch": event_ms})
 
-    gather_name = "gloo all-gather (one-GPU rehearsal)" if args.rehearse_one_gpu else "RCCL all-gather"
-    out = {
-        "metric": "MPC solves/sec (whole node), iiwa14 7-DOF, N=20",
-        "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": (f"BASELINE configs[2]: {B}-batch, randomized convex-set obstacles, N={N}, cold start, tol 1e-5, "
-                                "max_iter 100; a fresh batch every step" if world == 1 else
-                                f"BASELINE configs[3]: one {world * B}-batch (seed 65536) cut into {world} contiguous shards of {B}, "
-                                f"randomized convex-set obstacles, N={N}, cold start, {gather_name} of x"),
-                   "value_is": "inputs resident in HBM when the timed region starts, pipelined solver calls (solver_handles_in_flight / "
-                               "batches_per_solver_call): `value` EXCLUDES host<->device transfers.  The SURVEY 8(d) figure with the transfers "
-                               "inside the same schedule is value_pcie_inclusive_pipelined; value_single_batch / value_pcie_inclusive are one batch at a time",
-                   "batch_per_gpu": B, "horizon": N, "distinct_batches": n_distinct,
-                   "sharding": f"contiguous shards, no data-path collective, {gather_name} of x" if world > 1 else "single GPU",
-                   "hess": int(be.opts.hess), "solver_handles_in_flight": depth,
-                   "batches_per_solver_call": M, "batches_in_flight": depth * M, "pool_slots": args.pool},
+    out.update({
         "solver": {"iters_mean": mean_it, "iters_p50": float(np.median(it_np)), "iters_p99": float(np.percentile(it_np, 99)),
                    "iters_max": int(it_np.max()), "converged_frac": float((st_np == 0).mean()),
                    "accepted_frac": float(ok.mean()), "gen_s": t_gen, "stats_of": "the step-0 batch solved alone"},
@@ -379,7 +535,7 @@ def main():
         # the whole path against the same peak: SURVEY 8(d)'s flop model of a solve over the per-batch time of the timed region
         "valu_fp64": {"achieved": ach_tf, "peak": FP64_VEC_PEAK_TFLOPS, "unit": "TFLOP/s",
                       "frac": ach_tf / FP64_VEC_PEAK_TFLOPS, "alg_flops_per_solve": alg_flops_per_solve(N, mean_it)},
-    }
+    })
     if shard_check is not None:
         out["shard_check"] = shard_check
     if args.rehearse_one_gpu:

@@ -12,7 +12,7 @@ fi
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 tools/scaling_trace.py > $O/scaling_run.log 2>&1 || { tail $O/scaling_run.log; exit 1; }
 python3 tools/scaling_trace.py --parse $(find $O/trace -name "*kernel_trace.csv" | head -1) > $O/kernel_time_vs_live_instances.txt; rm -rf $O/trace
 cat $O/kernel_time_vs_live_instances.txt
-timeout -k 10 400 python3 bench.py --no-extra --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --no-extra --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python3 -c "
 import json,sys; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print({k:d[k] for k in ('value','ms_per_step') if k in d}, d.get('solver',{}))"
 if [ "$3" == "pmc" ]; then

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/prof_variant.sh NAME [bench args]  -> gpurun_out/kstat_NAME.csv (rocprofv3 kernel stats)
 NAME=$1; shift
+set -- --full "$@"      # kernel statistics of every leg of the bench line; the summary below reads its solver block
 export BMPC_LIB=$GRAFT_REPO_ROOT/build/variants/libboundmpc_$NAME.so
 [ "$NAME" = "default" ] && unset BMPC_LIB
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_round; rm -rf $O; mkdir -p $O
 ONE="--pool 0 --steps 2 --warmup 1 --depth 1 --merge 1 --same-batch --no-cpu-baseline --no-extra --gen-workers 0"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --gen-workers 0 --no-extra > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --gen-workers 0 --no-extra > $O/bench_default.json 2> $O/bench_default.err
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python3 bench.py $ONE > $O/bench_depth1.json 2> $O/bench_depth1.err
 cp $(find $O/stats1 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_depth1_merge1.csv
