@@ -4,6 +4,7 @@
 #define BMPC_NT 64
 #include "bmpc_pipeline.hpp"
 #include "bmpc_robot.hpp"
+#include "bmpc_ik.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -21,6 +22,9 @@ extern "C" hipError_t bmpc_launch_fk(int B, const RobotConst* rc, const double* 
                                      double* ee_rot, double* col_pts, double* jac, double* dvdq, hipStream_t st);
 
 extern "C" hipError_t bmpc_launch_spin(int ms, hipStream_t st);
+extern "C" hipError_t bmpc_launch_ik(int B, int log2s, const IkOpts* o, const RobotConst* rc, const double* pd, const double* rd,
+                                     const double* q0, const double* lo, const double* hi, double* q, double* cost, double* pos_err,
+                                     double* rot_err, int* iters, int* status, int* seed, hipStream_t st);
 
 extern "C" hipError_t bmpc_pipe_launch_init(const PipeArgsH* A, int n0, hipStream_t st);
 extern "C" hipError_t bmpc_pipe_launch_retire_out(const PipeArgsH* A, int n_max, hipStream_t st);
@@ -807,4 +811,90 @@ extern "C" int bmpc_debug_spin(bmpc_handle* h, int ms) {
     HIPCHK(h, hipSetDevice(h->o.device));
     HIPCHK(h, bmpc_launch_spin(ms, h->stream));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// batched inverse kinematics (bmpc_ik.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" void bmpc_default_ik_opts(bmpc_ik_opts* o) {
+    if (!o) return;
+    o->tol_cost = 1e-20; o->tol_grad = 1e-10; o->lambda0 = 1e-3; o->max_iter = 500;
+}
+
+// argument checks shared by both entries: 0 = go on, 1 = misuse (h->err set); *log2s = log2(n_seeds), *io = the options
+static int ik_check(bmpc_handle* h, const char* what, int B, int n_seeds, const bmpc_ik_opts* o, const void* pd, const void* rd,
+                    const void* q0, const void* q, int* log2s, IkOpts* io) {
+    if (B < 0 || !pd || !rd || !q0 || !q) { h->err = std::string(what) + ": null argument or B < 0"; return 1; }
+    if (n_seeds < 1 || n_seeds > 64 || (n_seeds & (n_seeds - 1))) {
+        h->err = std::string(what) + ": n_seeds must be a power of two in [1, 64]";
+        return 1;
+    }
+    if (B > (1 << 24)) { h->err = std::string(what) + ": B > 2^24"; return 1; }
+    bmpc_ik_opts d;
+    bmpc_default_ik_opts(&d);
+    if (o) d = *o;
+    if (!(d.lambda0 > 0.0) || !std::isfinite(d.lambda0)) { h->err = std::string(what) + ": lambda0 must be positive and finite"; return 1; }
+    *io = IkOpts{d.tol_cost, d.tol_grad, d.lambda0, d.max_iter};
+    int l = 0;
+    while ((1 << l) < n_seeds) l++;
+    *log2s = l;
+    return 0;
+}
+
+extern "C" int bmpc_ik_dev(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const double* d_pd, const double* d_rd,
+                           const double* d_q0, const double* d_lo, const double* d_hi, double* d_q, double* d_cost, double* d_pos_err,
+                           double* d_rot_err, int* d_iters, int* d_status, int* d_seed, void* stream) {
+    if (!h) return 1;
+    int log2s;
+    IkOpts io;
+    if (int r = ik_check(h, "bmpc_ik_dev", B, n_seeds, o, d_pd, d_rd, d_q0, d_q, &log2s, &io)) return r;
+    if (B == 0) return 0;
+    WEDGED_FAIL(h);
+    BUSY_OR_FAIL(h, "bmpc_ik_dev");       // an asynchronous solve in flight: 4 (nothing is waited for)
+    HIPCHK(h, hipSetDevice(h->o.device));
+    HIPCHK(h, bmpc_launch_ik(B, log2s, &io, h->d_rc, d_pd, d_rd, d_q0, d_lo, d_hi, d_q, d_cost, d_pos_err, d_rot_err, d_iters,
+                             d_status, d_seed, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int bmpc_ik(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const double* pd, const double* rd,
+                       const double* q0, const double* lo, const double* hi, double* q, double* cost, double* pos_err,
+                       double* rot_err, int* iters, int* status, int* seed) {
+    if (!h) return 1;
+    int log2s;
+    IkOpts io;
+    if (int r = ik_check(h, "bmpc_ik", B, n_seeds, o, pd, rd, q0, q, &log2s, &io)) return r;
+    if (B == 0) return 0;
+    WEDGED_FAIL(h);
+    BUSY_OR_FAIL(h, "bmpc_ik");
+    HIPCHK(h, hipSetDevice(h->o.device));
+    // one staging block per call: inputs pd 3, rd 9, q0 7, lo 7, hi 7; outputs q 7, cost, pos_err, rot_err; then 3 int arrays
+    const size_t nd = (size_t)B * (3 + 9 + 7 + 7 + 7 + 7 + 3), ni = (size_t)B * 3;
+    void* blk = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(h, hipMalloc(&blk, nd * sizeof(double) + ni * sizeof(int)));
+        double* d_pd = (double*)blk; double* d_rd = d_pd + (size_t)B * 3; double* d_q0 = d_rd + (size_t)B * 9;
+        double* d_lo = d_q0 + (size_t)B * 7; double* d_hi = d_lo + (size_t)B * 7; double* d_q = d_hi + (size_t)B * 7;
+        double* d_cost = d_q + (size_t)B * 7; double* d_pe = d_cost + B; double* d_re = d_pe + B;
+        int* d_it = (int*)(d_re + B); int* d_st = d_it + B; int* d_sd = d_st + B;
+        hipStream_t st = h->stream;
+        HIPCHK(h, hipMemcpyAsync(d_pd, pd, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_rd, rd, (size_t)B * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_q0, q0, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (lo) HIPCHK(h, hipMemcpyAsync(d_lo, lo, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (hi) HIPCHK(h, hipMemcpyAsync(d_hi, hi, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(h, bmpc_launch_ik(B, log2s, &io, h->d_rc, d_pd, d_rd, d_q0, lo ? d_lo : nullptr, hi ? d_hi : nullptr, d_q, d_cost, d_pe,
+                                 d_re, d_it, d_st, d_sd, st));
+        HIPCHK(h, hipMemcpyAsync(q, d_q, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (cost) HIPCHK(h, hipMemcpyAsync(cost, d_cost, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (pos_err) HIPCHK(h, hipMemcpyAsync(pos_err, d_pe, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (rot_err) HIPCHK(h, hipMemcpyAsync(rot_err, d_re, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (iters) HIPCHK(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (status) HIPCHK(h, hipMemcpyAsync(status, d_st, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (seed) HIPCHK(h, hipMemcpyAsync(seed, d_sd, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        return wait_stream(h, st);
+    };
+    const int rc = body();
+    if (blk && !h->wedged) (void)hipFree(blk);       // (after the watchdog fired queued work may still write it: leaked, as bmpc_destroy does)
+    return rc;
 }

@@ -16,6 +16,10 @@ _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
 
 
+class BmpcIkOpts(ctypes.Structure):
+    _fields_ = [("tol_cost", ctypes.c_double), ("tol_grad", ctypes.c_double), ("lambda0", ctypes.c_double), ("max_iter", ctypes.c_int)]
+
+
 class BmpcOpts(ctypes.Structure):
     _fields_ = [("N", ctypes.c_int), ("nr_segs", ctypes.c_int), ("dt", ctypes.c_double),
                 ("tol", ctypes.c_double), ("max_iter", ctypes.c_int), ("device", ctypes.c_int),
@@ -32,7 +36,8 @@ EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error"
            "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full", "bmpc_debug_lane_stats",
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
-           "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution"]
+           "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
+           "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev"]
 
 _lib = None
 
@@ -94,6 +99,9 @@ def load_library():
         lib.bmpc_loop_set_record.argtypes = [ctypes.c_void_p, ctypes.c_int, _ip]
         lib.bmpc_loop_records.argtypes = [ctypes.c_void_p, _dp, ctypes.c_int, _ip]
         lib.bmpc_loop_record_doubles.argtypes = [ctypes.c_int]
+        lib.bmpc_default_ik_opts.argtypes = [ctypes.POINTER(BmpcIkOpts)]
+        lib.bmpc_ik.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BmpcIkOpts)] + [_dp] * 9 + [_ip] * 3
+        lib.bmpc_ik_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BmpcIkOpts)] + [ctypes.c_void_p] * 13
         _lib = lib
     return _lib
 
@@ -243,6 +251,56 @@ class HipBoundMPC:
         self._chk(rc, "bmpc_fk")
         return out
 
+    def _ik_opts(self, opts):
+        o = BmpcIkOpts()
+        self.lib.bmpc_default_ik_opts(ctypes.byref(o))
+        for k, v in opts.items():
+            if k not in ("tol_cost", "tol_grad", "lambda0", "max_iter"):
+                raise TypeError(f"unknown IK option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def ik(self, pd, rd, q0, n_seeds=1, lo=None, hi=None, **opts):
+        """Batched inverse kinematics on the handle's robot (bmpc_ik): pd [B,3], rd [B,3,3], q0 [B,7]; lo / hi [B,7] (or [7]) or
+        None = the robot's limits; opts: tol_cost, tol_grad, lambda0, max_iter.  Returns q [B,7], cost, pos_err, rot_err, iters,
+        status, seed [B] (status 0 converged, 1 max_iter, 2 stalled, 3 numerical)."""
+        pd = np.ascontiguousarray(pd, float).reshape(-1, 3)
+        B = pd.shape[0]
+        rd = np.ascontiguousarray(rd, float).reshape(B, 9)
+        q0 = np.ascontiguousarray(q0, float).reshape(B, 7)
+        lo = None if lo is None else np.ascontiguousarray(np.broadcast_to(np.asarray(lo, float), (B, 7)))
+        hi = None if hi is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hi, float), (B, 7)))
+        out = dict(q=np.empty((B, 7)), cost=np.empty(B), pos_err=np.empty(B), rot_err=np.empty(B), iters=np.empty(B, np.int32),
+                   status=np.empty(B, np.int32), seed=np.empty(B, np.int32))
+        o = self._ik_opts(opts)
+        I = lambda a: a.ctypes.data_as(_ip)
+        rc = self.lib.bmpc_ik(self._h, B, int(n_seeds), ctypes.byref(o), _P(pd), _P(rd), _P(q0), _P(lo), _P(hi), _P(out["q"]),
+                              _P(out["cost"]), _P(out["pos_err"]), _P(out["rot_err"]), I(out["iters"]), I(out["status"]), I(out["seed"]))
+        self._chk(rc, "bmpc_ik")
+        return out
+
+    def ik_dev(self, pd, rd, q0, n_seeds=1, lo=None, hi=None, out=None, **opts):
+        """bmpc_ik_dev on torch tensors of the GPU (float64, contiguous: pd [B,3], rd [B,3,3], q0 [B,7], lo / hi [B,7] or None),
+        enqueued on torch.cuda.current_stream() without waiting.  out: dict of preallocated result tensors (the keys of ik) or None."""
+        import torch
+        B = pd.shape[0]
+        for name, t, shape in (("pd", pd, (B, 3)), ("rd", rd, (B, 3, 3)), ("q0", q0, (B, 7)), ("lo", lo, (B, 7)), ("hi", hi, (B, 7))):
+            if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError(f"ik_dev: {name} must be a contiguous float64 GPU tensor of shape {shape}")
+        if out is None:
+            kw = dict(device=pd.device)
+            out = dict(q=torch.empty((B, 7), dtype=torch.float64, **kw), cost=torch.empty(B, dtype=torch.float64, **kw),
+                       pos_err=torch.empty(B, dtype=torch.float64, **kw), rot_err=torch.empty(B, dtype=torch.float64, **kw),
+                       iters=torch.empty(B, dtype=torch.int32, **kw), status=torch.empty(B, dtype=torch.int32, **kw),
+                       seed=torch.empty(B, dtype=torch.int32, **kw))
+        o = self._ik_opts(opts)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self.lib.bmpc_ik_dev(self._h, B, int(n_seeds), ctypes.byref(o), ptr(pd), ptr(rd), ptr(q0), ptr(lo), ptr(hi), ptr(out["q"]),
+                                  ptr(out["cost"]), ptr(out["pos_err"]), ptr(out["rot_err"]), ptr(out["iters"]), ptr(out["status"]),
+                                  ptr(out["seed"]), torch.cuda.current_stream(pd.device).cuda_stream or None)
+        self._chk(rc, "bmpc_ik_dev")
+        return out
+
 
 class _DM:
     """Minimal stand-in for casadi.DM results: `.full()` and numpy conversion."""
@@ -285,6 +343,13 @@ class HipNlpSolver:
 
     def stats(self):
         return dict(self._stats)
+
+
+def default_ik_fn(robot=None):
+    """Batched inverse kinematics backed by the HIP library (used by RobotModel when no ik_fn is given): a function
+    (pd [B,3], rd [B,3,3], q0 [B,7], n_seeds=1) -> the dict of HipBoundMPC.ik."""
+    be = HipBoundMPC(15, robot=robot)
+    return lambda pd, rd, q0, n_seeds=1: be.ik(pd, rd, q0, n_seeds=n_seeds)
 
 
 def default_fk_fn():

@@ -155,6 +155,33 @@ int bmpc_active(bmpc_handle* h);
 int bmpc_fk(bmpc_handle* h, int B, const double* q, const double* dq, double* ee_pos,
             double* ee_rot, double* col_pts, double* jac, double* dvdq);
 
+/* Batched inverse kinematics: the problem of RobotModel.inverse_kinematics (RobotModel.py:79-144),
+ *   minimise_q |p_ee(q) - pd|^2 + |R_ee(q) rd^T - I|_F^2   subject to lo <= q <= hi,
+ * for B independent targets on the handle's robot (bmpc_set_robot), solved by a projected Levenberg-Marquardt method with n_seeds
+ * starts per target (a power of two in [1, 64]): seed 0 is q0, seed s >= 1 is point s of the 7-D Halton sequence (bases 2..17)
+ * mapped onto the box (lo + h (hi - lo); q0 + (2h - 1) pi on unlimited joints); the best seed by (status != 0, cost, index) is
+ * returned.  Host pointers: pd [B][3], rd [B][9] row-major (the user's matrix as passed), q0 [B][7]; lo / hi [B][7] or NULL = the
+ * robot's limits (+-1e20: unlimited).  Outputs q [B][7] (inside [lo, hi] exactly), cost [B], pos_err = |pd - p_ee(q)| [B],
+ * rot_err = |rotvec(R_ee(q) rd^T)| [B] (rad), iters [B] (trials, accepted or rejected), status [B] (0 converged: cost <= tol_cost
+ * or projected gradient <= tol_grad, 1 max_iter, 2 stalled, 3 numerical: a non-finite input, cost or step, or lo > hi), seed [B]
+ * (index of the winning start); any output but q may be NULL.  o == NULL: bmpc_default_ik_opts.  Return value: 0; 1 misuse
+ * (n_seeds, a null required pointer, B < 0, lambda0 <= 0; B == 0 does nothing), 4 the handle is busy (an asynchronous solve in
+ * flight), 5 the watchdog fired (the wait for the result uses bmpc_opts.watchdog_ms as bmpc_solve does). */
+typedef struct {
+    double tol_cost;    /* 1e-20 */
+    double tol_grad;    /* 1e-10: |P(q - grad J) - q|_inf, P = projection onto [lo, hi] */
+    double lambda0;     /* first Levenberg-Marquardt damping, 1e-3 */
+    int max_iter;       /* 500 (the reference's IPOPT max_iter) */
+} bmpc_ik_opts;
+void bmpc_default_ik_opts(bmpc_ik_opts* o);
+int bmpc_ik(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const double* pd, const double* rd, const double* q0,
+            const double* lo, const double* hi, double* q, double* cost, double* pos_err, double* rot_err, int* iters,
+            int* status, int* seed);
+/* Same with DEVICE pointers, enqueued on `stream` (a hipStream_t); returns without waiting. */
+int bmpc_ik_dev(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const double* d_pd, const double* d_rd,
+                const double* d_q0, const double* d_lo, const double* d_hi, double* d_q, double* d_cost, double* d_pos_err,
+                double* d_rot_err, int* d_iters, int* d_status, int* d_seed, void* stream);
+
 /* Duration (ms) of the most recent solve kernel measured with HIP events on its stream
  * (bmpc_solve: events around the launch; bmpc_solve_dev: caller must have synchronised). */
 int bmpc_last_kernel_ms(bmpc_handle* h, float* ms);
