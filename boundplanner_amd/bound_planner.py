@@ -54,7 +54,10 @@ def _shortest_path(adj, src, dst):
 
 class BoundPlanner:
     def __init__(self, obstacles=(), e_p_max=0.5, obs_size_increase=0.08, workspace_max=(1.0, 1.0, 1.2),
-                 workspace_min=(-1.0, -1.0, 0.0), seed=None):
+                 workspace_min=(-1.0, -1.0, 0.0), seed=None, set_backend=None):
+        """set_backend: batched convex-set backend (solver.default_sets_fn(), the HIP kernel) for the start set, the end set and the
+        samples of each round of the graph loop, or None: every set is grown on the host one at a time."""
+        self.set_backend = set_backend
         self.replanning = False
         self.sets_via_prev = []
         self.obs_size_increase = obs_size_increase
@@ -68,8 +71,19 @@ class BoundPlanner:
         self.obs, self.obs_sets, self.obs_sets_orig, self.obs_points_sets = [], [], [], []
         self.obs_points = np.empty((0, 3))
         self.add_obstacle_reps(obstacles)
-        self.set_finder = ConvexSetFinder(self.obs_sets, self.obs_points_sets, self.workspace_max, self.workspace_min)
+        self.set_finder = ConvexSetFinder(self.obs_sets, self.obs_points_sets, self.workspace_max, self.workspace_min,
+                                          sets_fn=set_backend)
         self.verbose = False
+
+    def _set_around_point(self, p, **kw):
+        if self.set_backend is None:
+            return self.set_finder.find_set_around_point(p, **kw)
+        return self.set_finder.find_sets_around_points([p], **kw)[0]
+
+    def _set_collision_avoidance(self, p0, p1):
+        if self.set_backend is None:
+            return self.set_finder.find_set_collision_avoidance(p0, p1, True)
+        return self.set_finder.find_sets_collision_avoidance([p0], [p1])[0]
 
     def _log(self, msg):
         if self.verbose:
@@ -273,15 +287,15 @@ class BoundPlanner:
             if new_obs:
                 h_idx = 1
             self.p_horizon_max = p_horizon[h_idx]
-            a_set, b_set, q_start, mid_start, collision = fnd.find_set_collision_avoidance(start, self.p_horizon_max, True)
+            a_set, b_set, q_start, mid_start, collision = self._set_collision_avoidance(start, self.p_horizon_max)
         else:
-            a_set, b_set, q_start, mid_start = fnd.find_set_around_point(start, fixed_mid=True)
+            a_set, b_set, q_start, mid_start = self._set_around_point(start, fixed_mid=True)
             if np.max(a_set @ (start + self.l_ee) - b_set) > 1e-8:
-                a_set, b_set, q_start, mid_start, collision = fnd.find_set_collision_avoidance(start, start + self.l_ee, True)
+                a_set, b_set, q_start, mid_start, collision = self._set_collision_avoidance(start, start + self.l_ee)
         if collision:
             if new_obs:
                 start = self._push_out_of_obstacles(start)
-                a_set, b_set, q_start, mid_start = fnd.find_set_around_point(start, fixed_mid=True)
+                a_set, b_set, q_start, mid_start = self._set_around_point(start, fixed_mid=True)
             else:       # no new set could be grown: keep the last set of the previous plan
                 a_set, b_set = copy.deepcopy(self.sets_via_prev[-1][0]), copy.deepcopy(self.sets_via_prev[-1][1])
                 mid_start, q_start = start, np.eye(3)
@@ -303,7 +317,7 @@ class BoundPlanner:
             return [start, end], r_via, [np.array([0, 0, 1.0])], sets_normed
 
         # ---- end set
-        a_set, b_set, q_end, mid_end, _ = fnd.find_set_collision_avoidance(end, end + self.l_ee_end, True)
+        a_set, b_set, q_end, mid_end, _ = self._set_collision_avoidance(end, end + self.l_ee_end)
         a_set, b_set = PO.reduce_ineqs(a_set, b_set)
         set_end = [a_set, b_set]
         v1 = self._new_vertex(G, set_end, q_end, mid_end, "Vertex end")
@@ -339,11 +353,16 @@ class BoundPlanner:
                 nr_samples += 1
                 if nr_samples > self.max_iters:
                     raise RuntimeError("(PosPath) Exceeded max iterations")
+            optimize = nr_samples < self.nr_optimized
+            if self.set_backend is not None:        # every set of the round in one batched call (each depends only on its seed)
+                round_sets = iter(fnd.find_sets_around_points(samples, fixed_mid=True, optimize=optimize))
             for sample in samples:
                 j += 1
-                optimize = nr_samples < self.nr_optimized
                 # (the reference builds a one-element tuple here, which is always true: BoundPlanner.py:503-505)
-                a_set, b_set, q_ell, p_mid = fnd.find_set_around_point(sample, fixed_mid=True, optimize=optimize)
+                if self.set_backend is None:
+                    a_set, b_set, q_ell, p_mid = fnd.find_set_around_point(sample, fixed_mid=True, optimize=optimize)
+                else:
+                    a_set, b_set, q_ell, p_mid = next(round_sets)
                 a_set, b_set = PO.reduce_ineqs(a_set, b_set)
                 sampled_first = True
                 d_known = min(np.linalg.norm(q_ell - v["q_ellipse"]) + np.linalg.norm(p_mid - v["p_mid"]) for v in G["v"])

@@ -20,7 +20,10 @@ def _inv_sym(q_inv):
 
 
 class ConvexSetFinder:
-    def __init__(self, obs_sets, obs_points_sets, e_max, e_min):
+    def __init__(self, obs_sets, obs_points_sets, e_max, e_min, sets_fn=None):
+        """sets_fn: batched backend of find_sets_around_points / find_sets_collision_avoidance (solver.default_sets_fn(), the HIP
+        kernel), or None: those loop over the single-set methods here."""
+        self.sets_fn = sets_fn
         self.obs_sets = [[np.asarray(a, float), np.asarray(b, float)] for a, b in obs_sets]
         self.obs_points_sets = [np.asarray(p, float) for p in obs_points_sets]
         self.e_max, self.e_min = np.asarray(e_max, float), np.asarray(e_min, float)
@@ -137,3 +140,32 @@ class ConvexSetFinder:
             q_ellipse, _ = _inv_sym(q_inv)
             return a_np, b_np, q_ellipse, p_mid, collision
         return a_np, b_np, collision
+
+    # -- batched forms: one call of the backend for many seeds (the sets depend only on their own seed)
+    def _batched(self, p0, p1=None, fixed_mid=False, optimize=True):
+        r = self.sets_fn(self.obs_sets, self.obs_points_sets, self.e_min, self.e_max, p0, p1, fixed_mid=fixed_mid, optimize=optimize)
+        r = {k: np.asarray(v) for k, v in r.items()}
+        bad = np.nonzero(r["status"] != 0)[0]
+        if bad.size:
+            from .solver import SETS_STATUS
+            st = int(r["status"][bad[0]])
+            raise RuntimeError(SETS_STATUS.get(st, f"convex set status {st}") + f" (seed {int(bad[0])})")
+        return r
+
+    def find_sets_around_points(self, points, fixed_mid=False, optimize=True):
+        """[find_set_around_point(p, fixed_mid, optimize) for p in points], through the batched backend when there is one."""
+        points = np.asarray(points, float).reshape(-1, 3)
+        if self.sets_fn is None:
+            return [self.find_set_around_point(p, fixed_mid=fixed_mid, optimize=optimize) for p in points]
+        r = self._batched(points, fixed_mid=fixed_mid, optimize=optimize)
+        return [(r["A"][k, :n].copy(), r["b"][k, :n].copy(), r["q_ellipse"][k].copy(), r["centre"][k].copy())
+                for k, n in enumerate(r["nrows"])]
+
+    def find_sets_collision_avoidance(self, p0s, p1s):
+        """[find_set_collision_avoidance(p0, p1, compute_ellipsoid=True) for p0, p1 in zip(p0s, p1s)], batched when possible."""
+        p0s, p1s = np.asarray(p0s, float).reshape(-1, 3), np.asarray(p1s, float).reshape(-1, 3)
+        if self.sets_fn is None:
+            return [self.find_set_collision_avoidance(a, b, compute_ellipsoid=True) for a, b in zip(p0s, p1s)]
+        r = self._batched(p0s, p1s)
+        return [(r["A"][k, :n].copy(), r["b"][k, :n].copy(), r["q_ellipse"][k].copy(), r["centre"][k].copy(), bool(r["collision"][k]))
+                for k, n in enumerate(r["nrows"])]

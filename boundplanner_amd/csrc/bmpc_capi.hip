@@ -5,6 +5,7 @@
 #include "bmpc_pipeline.hpp"
 #include "bmpc_robot.hpp"
 #include "bmpc_ik.hpp"
+#include "bmpc_sets.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -25,6 +26,10 @@ extern "C" hipError_t bmpc_launch_spin(int ms, hipStream_t st);
 extern "C" hipError_t bmpc_launch_ik(int B, int log2s, const IkOpts* o, const RobotConst* rc, const double* pd, const double* rd,
                                      const double* q0, const double* lo, const double* hi, double* q, double* cost, double* pos_err,
                                      double* rot_err, int* iters, int* status, int* seed, hipStream_t st);
+
+extern "C" hipError_t bmpc_launch_sets(int B, int segment, int fixed_mid, int optimize, const SetScene* sc, double* AAt_ws,
+                                       const double* p0, const double* p1, double* A, double* b, int* nrows, double* q, double* c,
+                                       int* rounds, int* newton, int* collision, int* status, hipStream_t st);
 
 extern "C" hipError_t bmpc_pipe_launch_init(const PipeArgsH* A, int n0, hipStream_t st);
 extern "C" hipError_t bmpc_pipe_launch_retire_out(const PipeArgsH* A, int n_max, hipStream_t st);
@@ -896,5 +901,113 @@ extern "C" int bmpc_ik(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o
     };
     const int rc = body();
     if (blk && !h->wedged) (void)hipFree(blk);       // (after the watchdog fired queued work may still write it: leaked, as bmpc_destroy does)
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// batched convex free-space sets (bmpc_sets.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" void bmpc_default_sets_opts(bmpc_sets_opts* o) {
+    if (!o) return;
+    o->segment = 0; o->fixed_mid = 0; o->optimize = 1;
+}
+
+// argument checks shared by both entries (host-visible values only: the obstacle tables of bmpc_convex_sets_dev are on the device)
+static int sets_check(bmpc_handle* h, const char* what, const bmpc_sets_opts* o, int n_obs, int B, bool ptrs_ok, bmpc_sets_opts* oo) {
+    if (B < 0 || !ptrs_ok) { h->err = std::string(what) + ": null argument or B < 0"; return 1; }
+    if (n_obs < 0 || n_obs > SETS_MAXOBS) { h->err = std::string(what) + ": n_obs must be in [0, 32]"; return 1; }
+    if (B > (1 << 24)) { h->err = std::string(what) + ": B > 2^24"; return 1; }
+    bmpc_default_sets_opts(oo);
+    if (o) *oo = *o;
+    return 0;
+}
+
+extern "C" int bmpc_convex_sets_dev(bmpc_handle* h, const bmpc_sets_opts* o, int n_obs, const double* d_obs_A, const double* d_obs_b,
+                                    const int* d_obs_nrows, const double* d_obs_V, const int* d_obs_nv, const double* d_e_min,
+                                    const double* d_e_max, int B, const double* d_p0, const double* d_p1, double* d_A, double* d_b,
+                                    int* d_nrows, double* d_q_ellipse, double* d_centre, int* d_rounds, int* d_newton, int* d_collision,
+                                    int* d_status, void* stream) {
+    if (!h) return 1;
+    bmpc_sets_opts so;
+    const bool ptrs = (n_obs == 0 || (d_obs_A && d_obs_b && d_obs_nrows && d_obs_V && d_obs_nv)) && d_e_min && d_e_max && d_p0 &&
+                      (!o || !o->segment || d_p1) && d_A && d_b && d_nrows && d_q_ellipse && d_centre && d_status;
+    if (int r = sets_check(h, "bmpc_convex_sets_dev", o, n_obs, B, ptrs, &so)) return r;
+    if (B == 0) return 0;
+    WEDGED_FAIL(h);
+    BUSY_OR_FAIL(h, "bmpc_convex_sets_dev");
+    HIPCHK(h, hipSetDevice(h->o.device));
+    hipStream_t st = (hipStream_t)stream;
+    // the workspace box is read by the kernel from its argument block: two small copies on the caller's stream
+    double box[6];
+    HIPCHK(h, hipMemcpyAsync(box, d_e_min, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(box + 3, d_e_max, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    SetScene sc{n_obs, d_obs_A, d_obs_b, d_obs_nrows, d_obs_V, d_obs_nv, nullptr, {box[0], box[1], box[2]}, {box[3], box[4], box[5]}};
+    double* ws = nullptr;                 // A A^T of the obstacles (segment mode), stream-ordered
+    if (so.segment && n_obs > 0) HIPCHK(h, hipMallocAsync((void**)&ws, (size_t)n_obs * SETS_OROWS * SETS_OROWS * sizeof(double), st));
+    HIPCHK(h, bmpc_launch_sets(B, so.segment != 0, so.fixed_mid != 0, so.optimize != 0, &sc, ws, d_p0, so.segment ? d_p1 : nullptr, d_A,
+                               d_b, d_nrows, d_q_ellipse, d_centre, d_rounds, d_newton, d_collision, d_status, st));
+    if (ws) HIPCHK(h, hipFreeAsync(ws, st));
+    return 0;
+}
+
+extern "C" int bmpc_convex_sets(bmpc_handle* h, const bmpc_sets_opts* o, int n_obs, const double* obs_A, const double* obs_b,
+                                const int* obs_nrows, const double* obs_V, const int* obs_nv, const double* e_min, const double* e_max,
+                                int B, const double* p0, const double* p1, double* A, double* b, int* nrows, double* q_ellipse,
+                                double* centre, int* rounds, int* newton, int* collision, int* status) {
+    if (!h) return 1;
+    bmpc_sets_opts so;
+    const bool ptrs = (n_obs == 0 || (obs_A && obs_b && obs_nrows && obs_V && obs_nv)) && e_min && e_max && p0 && (!o || !o->segment || p1) &&
+                      A && b && nrows && q_ellipse && centre && status;
+    if (int r = sets_check(h, "bmpc_convex_sets", o, n_obs, B, ptrs, &so)) return r;
+    for (int i = 0; i < n_obs; i++)
+        if (obs_nrows[i] < 0 || obs_nrows[i] > SETS_OROWS || obs_nv[i] < 1 || obs_nv[i] > SETS_NV) {
+            h->err = "bmpc_convex_sets: obstacle " + std::to_string(i) + ": rows must be in [0, 15], vertices in [1, 32]";
+            return 1;
+        }
+    if (B == 0) return 0;
+    WEDGED_FAIL(h);
+    BUSY_OR_FAIL(h, "bmpc_convex_sets");
+    HIPCHK(h, hipSetDevice(h->o.device));
+    const int no = n_obs > 0 ? n_obs : 1;
+    // one staging block per call: scene A 45, b 15, V 96, AAt 225 per obstacle; seeds p0, p1; outputs A 60, b 20, q 9, c 3; then the
+    // scene's 2 int arrays and 5 int outputs per instance
+    const size_t nsd = (size_t)no * (45 + 15 + 96 + 225), nd = nsd + (size_t)B * (3 + 3 + 60 + 20 + 9 + 3);
+    const size_t ni = (size_t)no * 2 + (size_t)B * 5;
+    void* blk = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(h, hipMalloc(&blk, nd * sizeof(double) + ni * sizeof(int)));
+        double* d_oA = (double*)blk; double* d_ob = d_oA + (size_t)no * 45; double* d_oV = d_ob + (size_t)no * 15;
+        double* d_aat = d_oV + (size_t)no * 96; double* d_p0 = d_aat + (size_t)no * 225; double* d_p1 = d_p0 + (size_t)B * 3;
+        double* d_A = d_p1 + (size_t)B * 3; double* d_b = d_A + (size_t)B * 60; double* d_q = d_b + (size_t)B * 20;
+        double* d_c = d_q + (size_t)B * 9;
+        int* d_onr = (int*)(d_c + (size_t)B * 3); int* d_onv = d_onr + no; int* d_nr = d_onv + no; int* d_rd = d_nr + B;
+        int* d_nw = d_rd + B; int* d_col = d_nw + B; int* d_st = d_col + B;
+        hipStream_t st = h->stream;
+        if (n_obs > 0) {
+            HIPCHK(h, hipMemcpyAsync(d_oA, obs_A, (size_t)n_obs * 45 * sizeof(double), hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(d_ob, obs_b, (size_t)n_obs * 15 * sizeof(double), hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(d_oV, obs_V, (size_t)n_obs * 96 * sizeof(double), hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(d_onr, obs_nrows, (size_t)n_obs * sizeof(int), hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(d_onv, obs_nv, (size_t)n_obs * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(h, hipMemcpyAsync(d_p0, p0, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (so.segment) HIPCHK(h, hipMemcpyAsync(d_p1, p1, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        SetScene sc{n_obs, d_oA, d_ob, d_onr, d_oV, d_onv, nullptr, {e_min[0], e_min[1], e_min[2]}, {e_max[0], e_max[1], e_max[2]}};
+        HIPCHK(h, bmpc_launch_sets(B, so.segment != 0, so.fixed_mid != 0, so.optimize != 0, &sc, d_aat, d_p0, so.segment ? d_p1 : nullptr,
+                                   d_A, d_b, d_nr, d_q, d_c, d_rd, d_nw, d_col, d_st, st));
+        HIPCHK(h, hipMemcpyAsync(A, d_A, (size_t)B * 60 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(b, d_b, (size_t)B * 20 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(q_ellipse, d_q, (size_t)B * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(centre, d_c, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(nrows, d_nr, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (rounds) HIPCHK(h, hipMemcpyAsync(rounds, d_rd, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (newton) HIPCHK(h, hipMemcpyAsync(newton, d_nw, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (collision) HIPCHK(h, hipMemcpyAsync(collision, d_col, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(status, d_st, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        return wait_stream(h, st);
+    };
+    const int rc = body();
+    if (blk && !h->wedged) (void)hipFree(blk);
     return rc;
 }

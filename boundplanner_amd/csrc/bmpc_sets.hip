@@ -1,0 +1,72 @@
+// Batched convex free-space sets (include/boundmpc.h bmpc_convex_sets): one thread per seed (point mode) or segment (segment mode),
+// the whole set growth inside one launch (body: bmpc_sets.hpp).  Lanes never exchange data, so a result does not depend on the batch
+// size or on the instance's position.  Storage: obstacle rows and vertices in global memory, read alike by
+// every lane; the set's rows in the lane's output rows; the per-obstacle distances of a round in LDS, [obstacle][lane].
+#include "bmpc_platform_hip.hpp"
+
+#define BMPC_NT 64
+#include "bmpc_sets.hpp"
+
+using namespace bmpc;
+
+constexpr int SETS_NT = 64;   // one wavefront per workgroup: 64 x 32 doubles of LDS (16 KiB)
+
+// A A^T of every obstacle (the segment mode's projections): one thread per (obstacle, row i)
+__global__ void bmpc_sets_aat_kernel(int n_obs, const double* A, const int* nrows, double* AAt) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_obs * SETS_OROWS) return;
+    const int o = t / SETS_OROWS, i = t % SETS_OROWS;
+    const double* a = A + 3 * SETS_OROWS * o;
+    for (int j = 0; j < SETS_OROWS; j++) {
+        double v = 0.0;
+        if (i < nrows[o] && j < nrows[o]) v = a[3 * i] * a[3 * j] + a[3 * i + 1] * a[3 * j + 1] + a[3 * i + 2] * a[3 * j + 2];
+        AAt[SETS_OROWS * SETS_OROWS * o + SETS_OROWS * i + j] = v;
+    }
+}
+
+__global__ __launch_bounds__(SETS_NT) void bmpc_sets_kernel(int B, int segment, int fixed_mid, int optimize, SetScene sc,
+                                                            const double* p0_, const double* p1_, double* A_out, double* b_out,
+                                                            int* nrows_out, double* q_out, double* c_out, int* rounds_out,
+                                                            int* newton_out, int* collision_out, int* status_out) {
+    __shared__ double sdist[SETS_MAXOBS * SETS_NT];
+    const long t = (long)blockIdx.x * SETS_NT + threadIdx.x;
+    if (t >= B) return;
+    double* A = A_out + t * SETS_ROWS * 3;
+    double* b = b_out + t * SETS_ROWS;
+    const double p0[3] = {p0_[3 * t], p0_[3 * t + 1], p0_[3 * t + 2]};
+    double qe[9], c[3];
+    SetResult r;
+    if (segment) {
+        const double p1[3] = {p1_[3 * t], p1_[3 * t + 1], p1_[3 * t + 2]};
+        r = sets_segment_lane(sc, p0, p1, sdist + threadIdx.x, SETS_NT, A, b, qe, c);
+    } else {
+        r = sets_point_lane(sc, p0, fixed_mid != 0, optimize != 0, sdist + threadIdx.x, SETS_NT, A, b, qe, c);
+    }
+    // rows past the set's (and all rows of a failed instance past what was written) are zero
+    const int n = r.status == SETS_OK ? r.nrows : 0;
+    for (int i = n; i < SETS_ROWS; i++) {
+        A[3 * i] = 0.0; A[3 * i + 1] = 0.0; A[3 * i + 2] = 0.0;
+        b[i] = 0.0;
+    }
+    for (int k = 0; k < 9; k++) q_out[9 * t + k] = qe[k];
+    for (int k = 0; k < 3; k++) c_out[3 * t + k] = c[k];
+    nrows_out[t] = n;
+    if (rounds_out) rounds_out[t] = r.rounds;
+    if (newton_out) newton_out[t] = r.newton;
+    if (collision_out) collision_out[t] = r.collision;
+    status_out[t] = r.status;
+}
+
+extern "C" hipError_t bmpc_launch_sets(int B, int segment, int fixed_mid, int optimize, const SetScene* sc, double* AAt_ws,
+                                       const double* p0, const double* p1, double* A, double* b, int* nrows, double* q, double* c,
+                                       int* rounds, int* newton, int* collision, int* status, hipStream_t st) {
+    SetScene s = *sc;
+    if (segment && s.n_obs > 0) {
+        const int n = s.n_obs * SETS_OROWS;
+        hipLaunchKernelGGL(bmpc_sets_aat_kernel, dim3((n + 63) / 64), dim3(64), 0, st, s.n_obs, s.A, s.nrows, AAt_ws);
+        s.AAt = AAt_ws;
+    }
+    hipLaunchKernelGGL(bmpc_sets_kernel, dim3((unsigned)((B + SETS_NT - 1) / SETS_NT)), dim3(SETS_NT), 0, st, B, segment, fixed_mid,
+                       optimize, s, p0, p1, A, b, nrows, q, c, rounds, newton, collision, status);
+    return hipGetLastError();
+}

@@ -20,6 +20,32 @@ class BmpcIkOpts(ctypes.Structure):
     _fields_ = [("tol_cost", ctypes.c_double), ("tol_grad", ctypes.c_double), ("lambda0", ctypes.c_double), ("max_iter", ctypes.c_int)]
 
 
+class BmpcSetsOpts(ctypes.Structure):
+    _fields_ = [("segment", ctypes.c_int), ("fixed_mid", ctypes.c_int), ("optimize", ctypes.c_int)]
+
+
+SETS_ROWS, SETS_MAXOBS, SETS_OROWS, SETS_NV = 20, 32, 15, 32       # include/boundmpc.h bmpc_convex_sets
+SETS_STATUS = {1: "Ellipse violates constraints", 2: "the set needs more than 20 rows", 3: "no strictly interior point for the ellipsoid",
+               4: "numerical failure"}
+
+
+def pack_set_scene(obs_sets, obs_points_sets):
+    """Obstacles as ConvexSetFinder holds them ([A, b] pairs and vertex arrays) in the layout of bmpc_convex_sets: A [n][15][3],
+    b [n][15], nrows [n], V [n][32][3], nv [n] (at most 32 obstacles, 15 rows and 32 vertices each)."""
+    n = len(obs_sets)
+    if n > SETS_MAXOBS or len(obs_points_sets) != n:
+        raise ValueError(f"at most {SETS_MAXOBS} obstacles, one vertex array per obstacle")
+    sc = dict(n_obs=n, A=np.zeros((max(n, 1), SETS_OROWS, 3)), b=np.zeros((max(n, 1), SETS_OROWS)), nrows=np.zeros(max(n, 1), np.int32),
+              V=np.zeros((max(n, 1), SETS_NV, 3)), nv=np.ones(max(n, 1), np.int32))
+    for i, ((a, b), v) in enumerate(zip(obs_sets, obs_points_sets)):
+        a, b, v = np.asarray(a, float).reshape(-1, 3), np.asarray(b, float).ravel(), np.asarray(v, float).reshape(-1, 3)
+        if a.shape[0] > SETS_OROWS or v.shape[0] > SETS_NV or v.shape[0] < 1:
+            raise ValueError(f"obstacle {i}: at most {SETS_OROWS} rows and 1..{SETS_NV} vertices")
+        sc["A"][i, :a.shape[0]], sc["b"][i, :a.shape[0]], sc["nrows"][i] = a, b, a.shape[0]
+        sc["V"][i, :v.shape[0]], sc["nv"][i] = v, v.shape[0]
+    return sc
+
+
 class BmpcOpts(ctypes.Structure):
     _fields_ = [("N", ctypes.c_int), ("nr_segs", ctypes.c_int), ("dt", ctypes.c_double),
                 ("tol", ctypes.c_double), ("max_iter", ctypes.c_int), ("device", ctypes.c_int),
@@ -37,7 +63,7 @@ EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error"
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
-           "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev"]
+           "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev", "bmpc_default_sets_opts", "bmpc_convex_sets", "bmpc_convex_sets_dev"]
 
 _lib = None
 
@@ -102,6 +128,11 @@ def load_library():
         lib.bmpc_default_ik_opts.argtypes = [ctypes.POINTER(BmpcIkOpts)]
         lib.bmpc_ik.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BmpcIkOpts)] + [_dp] * 9 + [_ip] * 3
         lib.bmpc_ik_dev.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BmpcIkOpts)] + [ctypes.c_void_p] * 13
+        lib.bmpc_default_sets_opts.argtypes = [ctypes.POINTER(BmpcSetsOpts)]
+        lib.bmpc_convex_sets.argtypes = [ctypes.c_void_p, ctypes.POINTER(BmpcSetsOpts), ctypes.c_int, _dp, _dp, _ip, _dp, _ip, _dp, _dp,
+                                         ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _ip]
+        lib.bmpc_convex_sets_dev.argtypes = [ctypes.c_void_p, ctypes.POINTER(BmpcSetsOpts), ctypes.c_int] + [ctypes.c_void_p] * 7 + \
+            [ctypes.c_int] + [ctypes.c_void_p] * 12
         _lib = lib
     return _lib
 
@@ -302,6 +333,69 @@ class HipBoundMPC:
         return out
 
 
+    def _sets_opts(self, segment, fixed_mid, optimize):
+        o = BmpcSetsOpts()
+        self.lib.bmpc_default_sets_opts(ctypes.byref(o))
+        o.segment, o.fixed_mid, o.optimize = int(bool(segment)), int(bool(fixed_mid)), int(bool(optimize))
+        return o
+
+    def convex_sets(self, obs_sets, obs_points_sets, e_min, e_max, p0, p1=None, fixed_mid=False, optimize=True):
+        """Batched convex free-space sets (bmpc_convex_sets): point mode (p1 None) grows the set of
+        ConvexSetFinder.find_set_around_point(p0[k], fixed_mid, optimize) around every row of p0 [B,3]; segment mode (p1 [B,3])
+        the set of find_set_collision_avoidance(p0[k], p1[k], compute_ellipsoid=True).  Obstacles as ConvexSetFinder holds them;
+        e_min / e_max: the workspace box.  Returns dict(A [B,20,3], b [B,20] (rows past nrows zero), nrows, q_ellipse [B,3,3],
+        centre [B,3], rounds, newton, collision, status [B]) -- status 0 ok, else a code of SETS_STATUS."""
+        sc = pack_set_scene(obs_sets, obs_points_sets)
+        p0 = np.ascontiguousarray(p0, float).reshape(-1, 3)
+        B = p0.shape[0]
+        p1 = None if p1 is None else np.ascontiguousarray(p1, float).reshape(B, 3)
+        e_min, e_max = (np.ascontiguousarray(e, float).reshape(3) for e in (e_min, e_max))
+        out = dict(A=np.empty((B, SETS_ROWS, 3)), b=np.empty((B, SETS_ROWS)), nrows=np.empty(B, np.int32), q_ellipse=np.empty((B, 3, 3)),
+                   centre=np.empty((B, 3)), rounds=np.empty(B, np.int32), newton=np.empty(B, np.int32), collision=np.empty(B, np.int32),
+                   status=np.empty(B, np.int32))
+        o = self._sets_opts(p1 is not None, fixed_mid, optimize)
+        I = lambda a: a.ctypes.data_as(_ip)
+        rc = self.lib.bmpc_convex_sets(self._h, ctypes.byref(o), sc["n_obs"], _P(sc["A"]), _P(sc["b"]), I(sc["nrows"]), _P(sc["V"]),
+                                       I(sc["nv"]), _P(e_min), _P(e_max), B, _P(p0), _P(p1), _P(out["A"]), _P(out["b"]), I(out["nrows"]),
+                                       _P(out["q_ellipse"]), _P(out["centre"]), I(out["rounds"]), I(out["newton"]), I(out["collision"]),
+                                       I(out["status"]))
+        self._chk(rc, "bmpc_convex_sets")
+        return out
+
+    def convex_sets_dev(self, scene, e_min, e_max, p0, p1=None, fixed_mid=False, optimize=True, out=None):
+        """bmpc_convex_sets_dev on torch tensors of the GPU, enqueued on torch.cuda.current_stream() without waiting.  scene: dict of
+        contiguous GPU tensors in the layout of pack_set_scene (A, b float64; nrows, nv int32; V float64) plus the int n_obs;
+        e_min / e_max: [3] float64 GPU tensors; p0 / p1: [B,3] float64.  out: dict of preallocated result tensors (the keys of
+        convex_sets) or None."""
+        import torch
+        B = p0.shape[0]
+        f64, i32 = torch.float64, torch.int32
+        chk = [("p0", p0, (B, 3), f64), ("p1", p1, (B, 3), f64), ("e_min", e_min, (3,), f64), ("e_max", e_max, (3,), f64)]
+        for k in ("A", "b", "V"):
+            chk.append((k, scene[k], tuple(scene[k].shape), f64))
+        for k in ("nrows", "nv"):
+            chk.append((k, scene[k], tuple(scene[k].shape), i32))
+        for name, t, shape, dt in chk:
+            if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError(f"convex_sets_dev: {name} must be a contiguous {dt} GPU tensor of shape {shape}")
+        if out is None:
+            kw = dict(device=p0.device)
+            out = dict(A=torch.empty((B, SETS_ROWS, 3), dtype=f64, **kw), b=torch.empty((B, SETS_ROWS), dtype=f64, **kw),
+                       nrows=torch.empty(B, dtype=i32, **kw), q_ellipse=torch.empty((B, 3, 3), dtype=f64, **kw),
+                       centre=torch.empty((B, 3), dtype=f64, **kw), rounds=torch.empty(B, dtype=i32, **kw),
+                       newton=torch.empty(B, dtype=i32, **kw), collision=torch.empty(B, dtype=i32, **kw),
+                       status=torch.empty(B, dtype=i32, **kw))
+        o = self._sets_opts(p1 is not None, fixed_mid, optimize)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = self.lib.bmpc_convex_sets_dev(self._h, ctypes.byref(o), int(scene["n_obs"]), ptr(scene["A"]), ptr(scene["b"]),
+                                           ptr(scene["nrows"]), ptr(scene["V"]), ptr(scene["nv"]), ptr(e_min), ptr(e_max), B, ptr(p0),
+                                           ptr(p1), ptr(out["A"]), ptr(out["b"]), ptr(out["nrows"]), ptr(out["q_ellipse"]),
+                                           ptr(out["centre"]), ptr(out["rounds"]), ptr(out["newton"]), ptr(out["collision"]),
+                                           ptr(out["status"]), torch.cuda.current_stream(p0.device).cuda_stream or None)
+        self._chk(rc, "bmpc_convex_sets_dev")
+        return out
+
+
 class _DM:
     """Minimal stand-in for casadi.DM results: `.full()` and numpy conversion."""
 
@@ -350,6 +444,14 @@ def default_ik_fn(robot=None):
     (pd [B,3], rd [B,3,3], q0 [B,7], n_seeds=1) -> the dict of HipBoundMPC.ik."""
     be = HipBoundMPC(15, robot=robot)
     return lambda pd, rd, q0, n_seeds=1: be.ik(pd, rd, q0, n_seeds=n_seeds)
+
+
+def default_sets_fn():
+    """Batched convex free-space sets backed by the HIP library (ConvexSetFinder(..., sets_fn=) / BoundPlanner(..., set_backend=)):
+    a function (obs_sets, obs_points_sets, e_min, e_max, p0 [B,3], p1=None, fixed_mid=False, optimize=True) -> the dict of
+    HipBoundMPC.convex_sets."""
+    be = HipBoundMPC(15)
+    return be.convex_sets
 
 
 def default_fk_fn():

@@ -182,6 +182,46 @@ int bmpc_ik_dev(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const
                 const double* d_q0, const double* d_lo, const double* d_hi, double* d_q, double* d_cost, double* d_pos_err,
                 double* d_rot_err, int* d_iters, int* d_status, int* d_seed, void* stream);
 
+/* Batched convex free-space sets of the plan phase (boundplanner_amd/convex_set_finder.py, reference ConvexSetFinder.py):
+ *   point mode:   the set of find_set_around_point(p0[k], fixed_mid, optimize) -- polyhedron growth around the seed in the metric of
+ *                 a maximum-volume inscribed ellipsoid, at most 5 rounds, until the ellipsoid's volume changes by less than 1 %;
+ *   segment mode: the set of find_set_collision_avoidance(p0[k], p1[k], compute_ellipsoid=True).
+ * One GPU thread per instance; an instance's result does not depend on B or on its position in the batch.
+ * Scene (host pointers): n_obs <= 32 obstacle polytopes {x: A x <= b}: obs_A [n_obs][15][3], obs_b [n_obs][15] (rows beyond
+ * obs_nrows[o] <= 15 are ignored), their vertices obs_V [n_obs][32][3] (obs_nv[o] in [1, 32] used); the workspace box e_min [3],
+ * e_max [3].  Seeds p0 [B][3]; segment mode also p1 [B][3].
+ * Outputs: A [B][20][3], b [B][20] (rows 0-5 the workspace box +x, -x, +y, -y, +z, -z, then the separating halfspaces nearest first;
+ * rows past nrows are zero), nrows [B], q_ellipse [B][9] (the host's q_ellipse: the inverse of L L^T of the ellipsoid
+ * {centre + L u: |u| <= 1}; with optimize = 0 the initial 1e4 I), centre [B][3], rounds [B] (polyhedra grown; 1 in segment mode),
+ * newton [B] (Newton steps of the ellipsoid solves), collision [B] (segment mode: the segment touches an obstacle), status [B]:
+ *   0 ok;
+ *   1 the nearest obstacle is closer than 0.99 in the ellipsoid's metric (the seed lies in or on an obstacle: the host raises
+ *     "Ellipse violates constraints");
+ *   2 the set would need more than 20 rows (nothing truncated: the instance has no set);
+ *   3 no strictly interior point for the ellipsoid (a fixed centre or seed outside the workspace box, or an empty set);
+ *   4 numerical: a non-finite seed, or a Newton system that is not positive definite.
+ * On status != 0, nrows is 0 and the rows are not meaningful.  rounds, newton and collision may be NULL.  o == NULL:
+ * bmpc_default_sets_opts.  Return value: 0; 1 misuse (a null required pointer, B < 0, n_obs, row or vertex counts out of range;
+ * B == 0 does nothing), 4 the handle is busy (an asynchronous solve in flight), 5 the watchdog fired (the wait uses
+ * bmpc_opts.watchdog_ms as bmpc_solve does). */
+typedef struct {
+    int segment;        /* 0: point mode (default), 1: segment mode (p1 required) */
+    int fixed_mid;      /* point mode: ellipsoids centred at the seed, a free-centre ellipsoid at the end (find_set_around_point) */
+    int optimize;       /* point mode: 0 returns the first polyhedron (around the 1e-2 ball), default 1 */
+} bmpc_sets_opts;
+void bmpc_default_sets_opts(bmpc_sets_opts* o);
+int bmpc_convex_sets(bmpc_handle* h, const bmpc_sets_opts* o, int n_obs, const double* obs_A, const double* obs_b, const int* obs_nrows,
+                     const double* obs_V, const int* obs_nv, const double* e_min, const double* e_max, int B, const double* p0,
+                     const double* p1, double* A, double* b, int* nrows, double* q_ellipse, double* centre, int* rounds, int* newton,
+                     int* collision, int* status);
+/* Same with DEVICE pointers for the scene, box, seeds and outputs, enqueued on `stream` (a hipStream_t); returns without waiting for
+ * the sets (it waits only for the 48-byte copy of e_min / e_max).  The obstacle counts are not checked on the host here: they must
+ * be in range. */
+int bmpc_convex_sets_dev(bmpc_handle* h, const bmpc_sets_opts* o, int n_obs, const double* d_obs_A, const double* d_obs_b,
+                         const int* d_obs_nrows, const double* d_obs_V, const int* d_obs_nv, const double* d_e_min, const double* d_e_max,
+                         int B, const double* d_p0, const double* d_p1, double* d_A, double* d_b, int* d_nrows, double* d_q_ellipse,
+                         double* d_centre, int* d_rounds, int* d_newton, int* d_collision, int* d_status, void* stream);
+
 /* Duration (ms) of the most recent solve kernel measured with HIP events on its stream
  * (bmpc_solve: events around the launch; bmpc_solve_dev: caller must have synchronised). */
 int bmpc_last_kernel_ms(bmpc_handle* h, float* ms);
