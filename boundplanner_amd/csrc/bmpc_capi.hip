@@ -1,118 +1,22 @@
-// libboundmpc_hip.so: C ABI (include/boundmpc.h) + kernel launches for gfx950.
+// libboundmpc_hip.so: C ABI (include/boundmpc.h) of the handle and the solver + the solver's launch sequence for gfx950.
+// The batched one-launch kernels' entries (bmpc_fk, bmpc_ik, bmpc_convex_sets): bmpc_capi_batch.hip.
 #include "bmpc_platform_hip.hpp"
 
 #define BMPC_NT 64
-#include "bmpc_pipeline.hpp"
-#include "bmpc_robot.hpp"
-#include "bmpc_ik.hpp"
-#include "bmpc_sets.hpp"
+#include "bmpc_handle.hpp"
+#include "bmpc_internal.hpp"
 
+#include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <atomic>
-#include <chrono>
-#include <string>
-#include <thread>
 #include <vector>
-
-#include "../../include/boundmpc.h"
 
 using namespace bmpc;
 
-extern "C" hipError_t bmpc_launch_fk(int B, const RobotConst* rc, const double* q, const double* dq, double* ee_pos,
-                                     double* ee_rot, double* col_pts, double* jac, double* dvdq, hipStream_t st);
-
-extern "C" hipError_t bmpc_launch_spin(int ms, hipStream_t st);
-extern "C" hipError_t bmpc_launch_ik(int B, int log2s, const IkOpts* o, const RobotConst* rc, const double* pd, const double* rd,
-                                     const double* q0, const double* lo, const double* hi, double* q, double* cost, double* pos_err,
-                                     double* rot_err, int* iters, int* status, int* seed, hipStream_t st);
-
-extern "C" hipError_t bmpc_launch_sets(int B, int segment, int fixed_mid, int optimize, const SetScene* sc, double* AAt_ws,
-                                       const double* p0, const double* p1, double* A, double* b, int* nrows, double* q, double* c,
-                                       int* rounds, int* newton, int* collision, int* status, hipStream_t st);
-
-extern "C" hipError_t bmpc_pipe_launch_init(const PipeArgsH* A, int n0, hipStream_t st);
-extern "C" hipError_t bmpc_pipe_launch_retire_out(const PipeArgsH* A, int n_max, hipStream_t st);
-extern "C" hipError_t bmpc_pipe_launch_retire_admit(const PipeArgsH* A, int n_max, int refill, hipStream_t st);
-// closed loop: called between the two halves of a retirement with the list of slots whose instances have just retired
-// (device pointers: list, its length); enqueues the caller's post-processing / next-problem kernels on the stream
-typedef int (*bmpc_retire_hook)(void* ctx, const int* d_done, const int* d_n_done, int n_max, void* stream);
-extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat);
-extern "C" hipError_t bmpc_pipe_launch_pick(PipeArgsH* A0, PipeArgsH* A1, const int* prio, int n_max, hipStream_t st);
-extern "C" hipError_t bmpc_pipe_launch_mult(const PipeArgsH* A, hipStream_t st);
-extern "C" void bmpc_pipe_build_table(int* tbl);
-extern "C" size_t bmpc_pipe_state_bytes(void);
-
-struct bmpc_handle {
-    bmpc_opts o;
-    int n_w, n_g, n_cu, nblocks_max;
-    RobotConst* d_rc = nullptr;
-    bmpc_robot robot;              // host copy of the robot table behind d_rc
-    double* d_prof = nullptr;   // diagnostic builds only
-    // workspace (grown on demand to the largest batch seen)
-    int pipe_cap = 0;
-    // workspace layout (pipe_carve): slot-major; BMPC_LAYOUT=0 in the environment selects the field-major layout of round 1 (A/B runs)
-    int slot_major = [] { const char* e = getenv("BMPC_LAYOUT"); return e ? atoi(e) : 1; }();
-    double* d_pipe = nullptr;      // one slab: SoA iterate/row arrays, stage records, gains, partials
-    void* d_pipe_st = nullptr;     // InstState[cap]
-    int* d_pipe_lists = nullptr;   // 8 lists + the slot -> row map of cap ints each + NCNT counters; then the same block again for
-                                   // the fast lane of the closed loop without lock step (pipe_solve)
-    int* d_pipe_tbl = nullptr;     // scatter table of the stage record
-    int* h_cnt = nullptr;          // pinned host copy of the counters (2 x NCNT: bulk lane, fast lane)
-    // closed loop without lock step, two lanes: streams of the fast lane / of the bulk lane (null: the caller's stream), fork / join events
-    hipStream_t st_fast = nullptr, st_bulk = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join_f = nullptr, ev_join_b = nullptr;
-    int lane_cfg[4] = {0, 0, 0, 0};         // [0] 1 = streams exist; what they were created for: [1] reserved CUs [2] fast lane on all CUs
-    double lane_stats[8] = {0};    // last hooked solve: [0] bursts [1] fast super-steps [2] bulk super-steps [3] sum of the fast lane's instance counts at its round ends [6] fast-lane rounds
-    int last_steps = 0;
-    PipeArgsH last_args;           // arguments of the most recent pipeline solve (its final iterate stays in the workspace)
-    bool last_valid = false;
-    double *d_lam_g = nullptr, *d_lam_x = nullptr;   // staging of the multipliers for the host-pointer entry
-    int cap_lam = 0;
-    // asynchronous solves: one in flight per handle, driven by a worker thread on the handle's stream
-    std::thread worker;
-    int worker_rc = 0;
-    std::atomic<int> n_active{0};  // unfinished instances of the solve in flight (updated at every readback)
-    // staging for the host-pointer entry
-    double *d_x0 = nullptr, *d_lbx = nullptr, *d_ubx = nullptr, *d_p = nullptr, *d_x = nullptr, *d_g = nullptr,
-           *d_f = nullptr, *d_viol = nullptr;
-    int *d_iters = nullptr, *d_status = nullptr;
-    int cap = 0;
-    bool cap_g = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_wait = nullptr;
-    // bmpc_debug_time_ric: HIP events around every launch of the Riccati kernel (the dominant kernel: bench.py's roofline leg)
-    bool time_ric = false;
-    hipEvent_t ric_ev[16] = {nullptr};      // 8 pairs: a burst has at most 8 super-steps and ends with a wait for the stream
-    int ric_pending = 0, ric_is_lat[8] = {0}, ric_nact[8] = {0};
-    int ric_full_n = 0;                     // grid size that counts as "the whole batch" (the first burst of a solve)
-    double ric_full[3] = {0, 0, 0};         // launches of bmpc_k_ric over the whole batch: summed duration [ms], launches, instance-iterations
-    double ric_ms[2] = {0, 0};              // [0] bmpc_k_ric, [1] bmpc_k_ric_lat: summed launch durations of the last solve
-    long ric_launches[2] = {0, 0}, ric_sweeps[2] = {0, 0};
-    bool wedged = false;           // a wait ran into the watchdog: the stream may still be busy, the handle refuses further work
-    float last_ms = 0.f;
-    std::atomic<bool> busy{false}; // a solve is running on this handle (a handle serves one host thread at a time)
-    std::atomic<int> n_loops{0};   // device loops borrowing this handle (bmpc_loop_create / bmpc_loop_destroy)
-    bool destroy_pending = false;  // bmpc_destroy called while loops were alive: the last loop frees the handle
-    std::string err;
-};
-
-#define HIPCHK(h, call)                                                                   \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                 \
-            return 2;                                                                     \
-        }                                                                                 \
-    } while (0)
-
 static int pipe_ensure(bmpc_handle* h, int B);
 
-// Wait for everything enqueued on `st` so far.  With bmpc_opts.watchdog_ms > 0 the wait polls an event and gives up after that
-// long: a kernel that does not return then costs the caller an error code -- rc 5, bmpc_last_error() --
-// instead of a host thread stuck in hipStreamSynchronize for ever.  The handle is unusable afterwards (its stream may never
-// drain): destroy it, or end the process when it does not come back.
-static int wait_stream(bmpc_handle* h, hipStream_t st) {
+// (contract: bmpc_handle.hpp)
+int wait_stream(bmpc_handle* h, hipStream_t st) {
     if (h->o.watchdog_ms <= 0) { HIPCHK(h, hipStreamSynchronize(st)); return 0; }
     HIPCHK(h, hipEventRecord(h->ev_wait, st));
     const auto t0 = std::chrono::steady_clock::now();
@@ -131,17 +35,6 @@ static int wait_stream(bmpc_handle* h, hipStream_t st) {
         else std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
 }
-#define WEDGED_FAIL(h) if ((h)->wedged) { (h)->err = "the handle ran into its watchdog earlier and is unusable"; return 5; }
-
-// one solve at a time per handle: a second host thread entering gets an error instead of a corrupted workspace
-struct BusyGuard {
-    bmpc_handle* h; bool ok;
-    explicit BusyGuard(bmpc_handle* h_) : h(h_) { bool f = false; ok = h->busy.compare_exchange_strong(f, true); }
-    ~BusyGuard() { if (ok) h->busy.store(false); }
-};
-#define BUSY_OR_FAIL(h, what)                                                                                   \
-    BusyGuard busy_guard_(h);                                                                                   \
-    if (!busy_guard_.ok) return 4;       /* (h->err belongs to the thread that owns the handle: not touched) */
 
 extern "C" void bmpc_default_opts(bmpc_opts* o, int N) {
     o->N = N; o->nr_segs = 4; o->dt = 0.1; o->tol = 1e-5; o->max_iter = 100; o->device = 0;
@@ -192,7 +85,7 @@ extern "C" int bmpc_create(const bmpc_opts* o, bmpc_handle** out) {
     return 0;
 }
 
-// device loops (bmpc_loop.hip) register with the handle they borrow, so that destroying the handle first is safe
+// (bmpc_internal.hpp)
 extern "C" void bmpc_handle_retain(bmpc_handle* h) { if (h) h->n_loops.fetch_add(1); }
 extern "C" void bmpc_handle_release(bmpc_handle* h) {
     if (!h) return;
@@ -297,6 +190,16 @@ extern "C" int bmpc_gbounds(const bmpc_handle* h, double* lbg, double* ubg) {
 // ------------------------------------------------------------------------------------------
 // workspace + launch sequence
 // ------------------------------------------------------------------------------------------
+// The work lists of one lane (pipe_solve) in its block of d_pipe_lists: 8 lists and the slot -> row map of `cap` ints each, then the
+// NCNT counters.  Returns the slot -> row map (both lanes work on the same slots: only the bulk lane's map is used).
+static size_t lane_list_ints(int cap) { return 9 * (size_t)cap + NCNT; }
+static int* lane_carve(ListsT<0>& L, int* base, int cap) {
+    const size_t c = (size_t)cap;
+    L.eval = base; L.step = base + c; L.trial = base + 2 * c; L.eval_next = base + 3 * c; L.trial_next = base + 4 * c;
+    L.done = base + 5 * c; L.admit = base + 6 * c; L.curv = base + 8 * c; L.cnt = base + 9 * c;
+    return base + 7 * c;
+}
+
 // workspace for `B` slots; a handle created with pool_slots > 0 never holds more than that many (larger batches stream
 // through the pool, bmpc_opts.pool_slots)
 static int pipe_ensure(bmpc_handle* h, int B) {
@@ -311,7 +214,7 @@ static int pipe_ensure(bmpc_handle* h, int B) {
     const size_t n = pipe_workspace_doubles(cap, h->o.N, h->slot_major);
     HIPCHK(h, hipMalloc((void**)&h->d_pipe, n * sizeof(double)));
     HIPCHK(h, hipMalloc((void**)&h->d_pipe_st, (size_t)cap * bmpc_pipe_state_bytes()));
-    HIPCHK(h, hipMalloc((void**)&h->d_pipe_lists, 2 * (9 * (size_t)cap + NCNT) * sizeof(int)));
+    HIPCHK(h, hipMalloc((void**)&h->d_pipe_lists, 2 * lane_list_ints(cap) * sizeof(int)));       // bulk lane, fast lane
     h->pipe_cap = cap;
     return 0;
 }
@@ -384,10 +287,7 @@ static int pipe_solve(bmpc_handle* h, int B, const double* d_x0, const double* d
     A.x = d_x; A.f = d_f; A.viol = d_viol; A.g = d_g; A.iters = d_iters; A.status = d_status;
     pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
     A.st = (InstState*)h->d_pipe_st;
-    int* L = h->d_pipe_lists;
-    A.L.eval = L; A.L.step = L + cap; A.L.trial = L + 2 * (size_t)cap; A.L.eval_next = L + 3 * (size_t)cap;
-    A.L.trial_next = L + 4 * (size_t)cap; A.L.done = L + 5 * (size_t)cap; A.L.admit = L + 6 * (size_t)cap;
-    A.src = L + 7 * (size_t)cap; A.L.curv = L + 8 * (size_t)cap; A.L.cnt = L + 9 * (size_t)cap;
+    A.src = lane_carve(A.L, h->d_pipe_lists, cap);
     A.tbl = h->d_pipe_tbl;
     A.prof = h->d_prof;
     A.lam_g = nullptr; A.lam_x = nullptr;
@@ -415,10 +315,7 @@ static int pipe_solve(bmpc_handle* h, int B, const double* d_x0, const double* d
     if (two) {
         if (int r = lanes_ensure(h, env_int("BMPC_FAST_CUS", 0), env_int("BMPC_FAST_ALL", 0))) return r;
         sf = h->st_fast; if (h->st_bulk) sb = h->st_bulk;
-        int* L1 = L + 9 * (size_t)cap + NCNT;
-        A1.L.eval = L1; A1.L.step = L1 + cap; A1.L.trial = L1 + 2 * (size_t)cap; A1.L.eval_next = L1 + 3 * (size_t)cap;
-        A1.L.trial_next = L1 + 4 * (size_t)cap; A1.L.done = L1 + 5 * (size_t)cap; A1.L.admit = L1 + 6 * (size_t)cap;
-        A1.L.curv = L1 + 8 * (size_t)cap; A1.L.cnt = L1 + 9 * (size_t)cap;
+        lane_carve(A1.L, h->d_pipe_lists + lane_list_ints(cap), cap);
         HIPCHK(h, hipMemsetAsync(A1.L.cnt, 0, NCNT * sizeof(int), st));
     }
     if (hook) for (double& v : h->lane_stats) v = 0;
@@ -547,8 +444,7 @@ extern "C" int bmpc_solve_dev(bmpc_handle* h, int B, const double* d_x0, const d
     return launch(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, d_g, d_f, d_iters, d_status, d_viol, (hipStream_t)stream);
 }
 
-// Closed loop without lock step (bmpc_loop_run_async): B rows, each a rollout whose successive problems are produced in
-// place by `hook`; a row is solved again while d_cont[row] != 0.  Internal to the library (bmpc_loop.hip).
+// (bmpc_internal.hpp; called by bmpc_loop.hip)
 extern "C" int bmpc_solve_dev_hooked(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx,
                                      const double* d_p, double* d_x, double* d_f, int* d_iters, int* d_status, double* d_viol,
                                      void* stream, bmpc_retire_hook hook, void* hook_ctx, const int* d_cont,
@@ -710,38 +606,6 @@ extern "C" int bmpc_last_kernel_ms(bmpc_handle* h, float* ms) {
     return 0;
 }
 
-extern "C" int bmpc_fk(bmpc_handle* h, int B, const double* q, const double* dq, double* ee_pos,
-                       double* ee_rot, double* col_pts, double* jac, double* dvdq) {
-    if (!h || B < 0 || !q) { if (h) h->err = "bmpc_fk: null argument"; return 1; }
-    if (B == 0) return 0;
-    HIPCHK(h, hipSetDevice(h->o.device));
-    double *d_q = nullptr, *d_dq = nullptr, *d_out = nullptr;
-    const size_t per = 3 + 9 + 18 + 42 + 42;
-    auto body = [&]() -> int {
-        HIPCHK(h, hipMalloc((void**)&d_q, (size_t)B * 7 * sizeof(double)));
-        HIPCHK(h, hipMalloc((void**)&d_dq, (size_t)B * 7 * sizeof(double)));
-        HIPCHK(h, hipMalloc((void**)&d_out, (size_t)B * per * sizeof(double)));
-        HIPCHK(h, hipMemcpy(d_q, q, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice));
-        if (dq) HIPCHK(h, hipMemcpy(d_dq, dq, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice));
-        else HIPCHK(h, hipMemset(d_dq, 0, (size_t)B * 7 * sizeof(double)));
-        double* o_pos = d_out; double* o_rot = o_pos + (size_t)B * 3; double* o_col = o_rot + (size_t)B * 9;
-        double* o_jac = o_col + (size_t)B * 18; double* o_dv = o_jac + (size_t)B * 42;
-        HIPCHK(h, bmpc_launch_fk(B, h->d_rc, d_q, d_dq, o_pos, o_rot, o_col, o_jac, o_dv, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (ee_pos) HIPCHK(h, hipMemcpy(ee_pos, o_pos, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost));
-        if (ee_rot) HIPCHK(h, hipMemcpy(ee_rot, o_rot, (size_t)B * 9 * sizeof(double), hipMemcpyDeviceToHost));
-        if (col_pts) HIPCHK(h, hipMemcpy(col_pts, o_col, (size_t)B * 18 * sizeof(double), hipMemcpyDeviceToHost));
-        if (jac) HIPCHK(h, hipMemcpy(jac, o_jac, (size_t)B * 42 * sizeof(double), hipMemcpyDeviceToHost));
-        if (dvdq) HIPCHK(h, hipMemcpy(dvdq, o_dv, (size_t)B * 42 * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();          // temporaries are freed on the error paths too
-    if (d_q) (void)hipFree(d_q);
-    if (d_dq) (void)hipFree(d_dq);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
-}
-
 // diagnostic: per-phase cycle sums accumulated by a -DBMPC_PROFILE build (zeros otherwise)
 extern "C" int bmpc_debug_phase_cycles(bmpc_handle* h, double* out16) {
     if (!h || !out16) return 1;
@@ -803,211 +667,17 @@ extern "C" int bmpc_debug_ric_stats(bmpc_handle* h, double* out6) {
     return 0;
 }
 
-// diagnostic: keep the handle's stream busy for `ms` milliseconds (at most 10 s) -- lets a test exercise the watchdog
 extern "C" int bmpc_debug_ric_stats_full(bmpc_handle* h, double* out3) {
     if (!h || !out3) return 1;
     for (int i = 0; i < 3; i++) out3[i] = h->ric_full[i];
     return 0;
 }
 
+// diagnostic: keep the handle's stream busy for `ms` milliseconds (at most 10 s) -- lets a test exercise the watchdog
 extern "C" int bmpc_debug_spin(bmpc_handle* h, int ms) {
     if (!h) return 1;
     WEDGED_FAIL(h);
     HIPCHK(h, hipSetDevice(h->o.device));
     HIPCHK(h, bmpc_launch_spin(ms, h->stream));
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// batched inverse kinematics (bmpc_ik.hip)
-// ------------------------------------------------------------------------------------------
-extern "C" void bmpc_default_ik_opts(bmpc_ik_opts* o) {
-    if (!o) return;
-    o->tol_cost = 1e-20; o->tol_grad = 1e-10; o->lambda0 = 1e-3; o->max_iter = 500;
-}
-
-// argument checks shared by both entries: 0 = go on, 1 = misuse (h->err set); *log2s = log2(n_seeds), *io = the options
-static int ik_check(bmpc_handle* h, const char* what, int B, int n_seeds, const bmpc_ik_opts* o, const void* pd, const void* rd,
-                    const void* q0, const void* q, int* log2s, IkOpts* io) {
-    if (B < 0 || !pd || !rd || !q0 || !q) { h->err = std::string(what) + ": null argument or B < 0"; return 1; }
-    if (n_seeds < 1 || n_seeds > 64 || (n_seeds & (n_seeds - 1))) {
-        h->err = std::string(what) + ": n_seeds must be a power of two in [1, 64]";
-        return 1;
-    }
-    if (B > (1 << 24)) { h->err = std::string(what) + ": B > 2^24"; return 1; }
-    bmpc_ik_opts d;
-    bmpc_default_ik_opts(&d);
-    if (o) d = *o;
-    if (!(d.lambda0 > 0.0) || !std::isfinite(d.lambda0)) { h->err = std::string(what) + ": lambda0 must be positive and finite"; return 1; }
-    *io = IkOpts{d.tol_cost, d.tol_grad, d.lambda0, d.max_iter};
-    int l = 0;
-    while ((1 << l) < n_seeds) l++;
-    *log2s = l;
-    return 0;
-}
-
-extern "C" int bmpc_ik_dev(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const double* d_pd, const double* d_rd,
-                           const double* d_q0, const double* d_lo, const double* d_hi, double* d_q, double* d_cost, double* d_pos_err,
-                           double* d_rot_err, int* d_iters, int* d_status, int* d_seed, void* stream) {
-    if (!h) return 1;
-    int log2s;
-    IkOpts io;
-    if (int r = ik_check(h, "bmpc_ik_dev", B, n_seeds, o, d_pd, d_rd, d_q0, d_q, &log2s, &io)) return r;
-    if (B == 0) return 0;
-    WEDGED_FAIL(h);
-    BUSY_OR_FAIL(h, "bmpc_ik_dev");       // an asynchronous solve in flight: 4 (nothing is waited for)
-    HIPCHK(h, hipSetDevice(h->o.device));
-    HIPCHK(h, bmpc_launch_ik(B, log2s, &io, h->d_rc, d_pd, d_rd, d_q0, d_lo, d_hi, d_q, d_cost, d_pos_err, d_rot_err, d_iters,
-                             d_status, d_seed, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int bmpc_ik(bmpc_handle* h, int B, int n_seeds, const bmpc_ik_opts* o, const double* pd, const double* rd,
-                       const double* q0, const double* lo, const double* hi, double* q, double* cost, double* pos_err,
-                       double* rot_err, int* iters, int* status, int* seed) {
-    if (!h) return 1;
-    int log2s;
-    IkOpts io;
-    if (int r = ik_check(h, "bmpc_ik", B, n_seeds, o, pd, rd, q0, q, &log2s, &io)) return r;
-    if (B == 0) return 0;
-    WEDGED_FAIL(h);
-    BUSY_OR_FAIL(h, "bmpc_ik");
-    HIPCHK(h, hipSetDevice(h->o.device));
-    // one staging block per call: inputs pd 3, rd 9, q0 7, lo 7, hi 7; outputs q 7, cost, pos_err, rot_err; then 3 int arrays
-    const size_t nd = (size_t)B * (3 + 9 + 7 + 7 + 7 + 7 + 3), ni = (size_t)B * 3;
-    void* blk = nullptr;
-    auto body = [&]() -> int {
-        HIPCHK(h, hipMalloc(&blk, nd * sizeof(double) + ni * sizeof(int)));
-        double* d_pd = (double*)blk; double* d_rd = d_pd + (size_t)B * 3; double* d_q0 = d_rd + (size_t)B * 9;
-        double* d_lo = d_q0 + (size_t)B * 7; double* d_hi = d_lo + (size_t)B * 7; double* d_q = d_hi + (size_t)B * 7;
-        double* d_cost = d_q + (size_t)B * 7; double* d_pe = d_cost + B; double* d_re = d_pe + B;
-        int* d_it = (int*)(d_re + B); int* d_st = d_it + B; int* d_sd = d_st + B;
-        hipStream_t st = h->stream;
-        HIPCHK(h, hipMemcpyAsync(d_pd, pd, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d_rd, rd, (size_t)B * 9 * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d_q0, q0, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-        if (lo) HIPCHK(h, hipMemcpyAsync(d_lo, lo, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-        if (hi) HIPCHK(h, hipMemcpyAsync(d_hi, hi, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(h, bmpc_launch_ik(B, log2s, &io, h->d_rc, d_pd, d_rd, d_q0, lo ? d_lo : nullptr, hi ? d_hi : nullptr, d_q, d_cost, d_pe,
-                                 d_re, d_it, d_st, d_sd, st));
-        HIPCHK(h, hipMemcpyAsync(q, d_q, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (cost) HIPCHK(h, hipMemcpyAsync(cost, d_cost, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (pos_err) HIPCHK(h, hipMemcpyAsync(pos_err, d_pe, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (rot_err) HIPCHK(h, hipMemcpyAsync(rot_err, d_re, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (iters) HIPCHK(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (status) HIPCHK(h, hipMemcpyAsync(status, d_st, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (seed) HIPCHK(h, hipMemcpyAsync(seed, d_sd, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        return wait_stream(h, st);
-    };
-    const int rc = body();
-    if (blk && !h->wedged) (void)hipFree(blk);       // (after the watchdog fired queued work may still write it: leaked, as bmpc_destroy does)
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------------
-// batched convex free-space sets (bmpc_sets.hip)
-// ------------------------------------------------------------------------------------------
-extern "C" void bmpc_default_sets_opts(bmpc_sets_opts* o) {
-    if (!o) return;
-    o->segment = 0; o->fixed_mid = 0; o->optimize = 1;
-}
-
-// argument checks shared by both entries (host-visible values only: the obstacle tables of bmpc_convex_sets_dev are on the device)
-static int sets_check(bmpc_handle* h, const char* what, const bmpc_sets_opts* o, int n_obs, int B, bool ptrs_ok, bmpc_sets_opts* oo) {
-    if (B < 0 || !ptrs_ok) { h->err = std::string(what) + ": null argument or B < 0"; return 1; }
-    if (n_obs < 0 || n_obs > SETS_MAXOBS) { h->err = std::string(what) + ": n_obs must be in [0, 32]"; return 1; }
-    if (B > (1 << 24)) { h->err = std::string(what) + ": B > 2^24"; return 1; }
-    bmpc_default_sets_opts(oo);
-    if (o) *oo = *o;
-    return 0;
-}
-
-extern "C" int bmpc_convex_sets_dev(bmpc_handle* h, const bmpc_sets_opts* o, int n_obs, const double* d_obs_A, const double* d_obs_b,
-                                    const int* d_obs_nrows, const double* d_obs_V, const int* d_obs_nv, const double* d_e_min,
-                                    const double* d_e_max, int B, const double* d_p0, const double* d_p1, double* d_A, double* d_b,
-                                    int* d_nrows, double* d_q_ellipse, double* d_centre, int* d_rounds, int* d_newton, int* d_collision,
-                                    int* d_status, void* stream) {
-    if (!h) return 1;
-    bmpc_sets_opts so;
-    const bool ptrs = (n_obs == 0 || (d_obs_A && d_obs_b && d_obs_nrows && d_obs_V && d_obs_nv)) && d_e_min && d_e_max && d_p0 &&
-                      (!o || !o->segment || d_p1) && d_A && d_b && d_nrows && d_q_ellipse && d_centre && d_status;
-    if (int r = sets_check(h, "bmpc_convex_sets_dev", o, n_obs, B, ptrs, &so)) return r;
-    if (B == 0) return 0;
-    WEDGED_FAIL(h);
-    BUSY_OR_FAIL(h, "bmpc_convex_sets_dev");
-    HIPCHK(h, hipSetDevice(h->o.device));
-    hipStream_t st = (hipStream_t)stream;
-    // the workspace box is read by the kernel from its argument block: two small copies on the caller's stream
-    double box[6];
-    HIPCHK(h, hipMemcpyAsync(box, d_e_min, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(box + 3, d_e_max, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    SetScene sc{n_obs, d_obs_A, d_obs_b, d_obs_nrows, d_obs_V, d_obs_nv, nullptr, {box[0], box[1], box[2]}, {box[3], box[4], box[5]}};
-    double* ws = nullptr;                 // A A^T of the obstacles (segment mode), stream-ordered
-    if (so.segment && n_obs > 0) HIPCHK(h, hipMallocAsync((void**)&ws, (size_t)n_obs * SETS_OROWS * SETS_OROWS * sizeof(double), st));
-    HIPCHK(h, bmpc_launch_sets(B, so.segment != 0, so.fixed_mid != 0, so.optimize != 0, &sc, ws, d_p0, so.segment ? d_p1 : nullptr, d_A,
-                               d_b, d_nrows, d_q_ellipse, d_centre, d_rounds, d_newton, d_collision, d_status, st));
-    if (ws) HIPCHK(h, hipFreeAsync(ws, st));
-    return 0;
-}
-
-extern "C" int bmpc_convex_sets(bmpc_handle* h, const bmpc_sets_opts* o, int n_obs, const double* obs_A, const double* obs_b,
-                                const int* obs_nrows, const double* obs_V, const int* obs_nv, const double* e_min, const double* e_max,
-                                int B, const double* p0, const double* p1, double* A, double* b, int* nrows, double* q_ellipse,
-                                double* centre, int* rounds, int* newton, int* collision, int* status) {
-    if (!h) return 1;
-    bmpc_sets_opts so;
-    const bool ptrs = (n_obs == 0 || (obs_A && obs_b && obs_nrows && obs_V && obs_nv)) && e_min && e_max && p0 && (!o || !o->segment || p1) &&
-                      A && b && nrows && q_ellipse && centre && status;
-    if (int r = sets_check(h, "bmpc_convex_sets", o, n_obs, B, ptrs, &so)) return r;
-    for (int i = 0; i < n_obs; i++)
-        if (obs_nrows[i] < 0 || obs_nrows[i] > SETS_OROWS || obs_nv[i] < 1 || obs_nv[i] > SETS_NV) {
-            h->err = "bmpc_convex_sets: obstacle " + std::to_string(i) + ": rows must be in [0, 15], vertices in [1, 32]";
-            return 1;
-        }
-    if (B == 0) return 0;
-    WEDGED_FAIL(h);
-    BUSY_OR_FAIL(h, "bmpc_convex_sets");
-    HIPCHK(h, hipSetDevice(h->o.device));
-    const int no = n_obs > 0 ? n_obs : 1;
-    // one staging block per call: scene A 45, b 15, V 96, AAt 225 per obstacle; seeds p0, p1; outputs A 60, b 20, q 9, c 3; then the
-    // scene's 2 int arrays and 5 int outputs per instance
-    const size_t nsd = (size_t)no * (45 + 15 + 96 + 225), nd = nsd + (size_t)B * (3 + 3 + 60 + 20 + 9 + 3);
-    const size_t ni = (size_t)no * 2 + (size_t)B * 5;
-    void* blk = nullptr;
-    auto body = [&]() -> int {
-        HIPCHK(h, hipMalloc(&blk, nd * sizeof(double) + ni * sizeof(int)));
-        double* d_oA = (double*)blk; double* d_ob = d_oA + (size_t)no * 45; double* d_oV = d_ob + (size_t)no * 15;
-        double* d_aat = d_oV + (size_t)no * 96; double* d_p0 = d_aat + (size_t)no * 225; double* d_p1 = d_p0 + (size_t)B * 3;
-        double* d_A = d_p1 + (size_t)B * 3; double* d_b = d_A + (size_t)B * 60; double* d_q = d_b + (size_t)B * 20;
-        double* d_c = d_q + (size_t)B * 9;
-        int* d_onr = (int*)(d_c + (size_t)B * 3); int* d_onv = d_onr + no; int* d_nr = d_onv + no; int* d_rd = d_nr + B;
-        int* d_nw = d_rd + B; int* d_col = d_nw + B; int* d_st = d_col + B;
-        hipStream_t st = h->stream;
-        if (n_obs > 0) {
-            HIPCHK(h, hipMemcpyAsync(d_oA, obs_A, (size_t)n_obs * 45 * sizeof(double), hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(d_ob, obs_b, (size_t)n_obs * 15 * sizeof(double), hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(d_oV, obs_V, (size_t)n_obs * 96 * sizeof(double), hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(d_onr, obs_nrows, (size_t)n_obs * sizeof(int), hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(d_onv, obs_nv, (size_t)n_obs * sizeof(int), hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(h, hipMemcpyAsync(d_p0, p0, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        if (so.segment) HIPCHK(h, hipMemcpyAsync(d_p1, p1, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        SetScene sc{n_obs, d_oA, d_ob, d_onr, d_oV, d_onv, nullptr, {e_min[0], e_min[1], e_min[2]}, {e_max[0], e_max[1], e_max[2]}};
-        HIPCHK(h, bmpc_launch_sets(B, so.segment != 0, so.fixed_mid != 0, so.optimize != 0, &sc, d_aat, d_p0, so.segment ? d_p1 : nullptr,
-                                   d_A, d_b, d_nr, d_q, d_c, d_rd, d_nw, d_col, d_st, st));
-        HIPCHK(h, hipMemcpyAsync(A, d_A, (size_t)B * 60 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(b, d_b, (size_t)B * 20 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(q_ellipse, d_q, (size_t)B * 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(centre, d_c, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(nrows, d_nr, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (rounds) HIPCHK(h, hipMemcpyAsync(rounds, d_rd, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (newton) HIPCHK(h, hipMemcpyAsync(newton, d_nw, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (collision) HIPCHK(h, hipMemcpyAsync(collision, d_col, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(status, d_st, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        return wait_stream(h, st);
-    };
-    const int rc = body();
-    if (blk && !h->wedged) (void)hipFree(blk);
-    return rc;
 }

@@ -2,6 +2,7 @@
 #include "bmpc_platform_hip.hpp"
 
 #include "bmpc_device.hpp"
+#include "bmpc_internal.hpp"
 
 using namespace bmpc;
 

@@ -4,6 +4,7 @@
 #include "bmpc_platform_hip.hpp"
 
 #include "bmpc_ik.hpp"
+#include "bmpc_internal.hpp"
 
 using namespace bmpc;
 
@@ -39,17 +40,7 @@ __global__ __launch_bounds__(IK_NT, 2) void bmpc_ik_kernel(int B, int log2s, IkO
         if (ik_better(ost, of, os, bst, bf, bs)) { bst = ost; bf = of; bs = os; }
     }
     if (s != bs) return;
-    for (int j = 0; j < 7; j++) q_out[b * 7 + j] = q[j];
-    if (cost_out) cost_out[b] = cost;
-    if (iters_out) iters_out[b] = iters;
-    if (status_out) status_out[b] = status;
-    if (seed_out) seed_out[b] = s;
-    if (perr_out || rerr_out) {
-        double pe, re;
-        ik_eval<false>(rc, q, pd, rd, nullptr, nullptr, &pe, &re);
-        if (perr_out) perr_out[b] = pe;
-        if (rerr_out) rerr_out[b] = re;
-    }
+    ik_store(rc, b, s, q, cost, iters, status, pd, rd, q_out, cost_out, perr_out, rerr_out, iters_out, status_out, seed_out);
 }
 
 extern "C" hipError_t bmpc_launch_ik(int B, int log2s, const IkOpts* o, const RobotConst* rc, const double* pd, const double* rd,

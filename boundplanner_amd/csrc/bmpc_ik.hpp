@@ -226,4 +226,21 @@ BMPC_INL bool ik_better(int st_a, double f_a, int s_a, int st_b, double f_b, int
     return s_a < s_b;
 }
 
+// outputs of instance b from its best seed s (ik_better); every output but q_out may be null; the errors are evaluated at q again
+BMPC_INL void ik_store(const RobotConst* rc, long b, int s, const double* q, double cost, int iters, int status, const double* pd,
+                       const double* rd, double* q_out, double* cost_out, double* perr_out, double* rerr_out, int* iters_out,
+                       int* status_out, int* seed_out) {
+    for (int j = 0; j < 7; j++) q_out[b * 7 + j] = q[j];
+    if (cost_out) cost_out[b] = cost;
+    if (iters_out) iters_out[b] = iters;
+    if (status_out) status_out[b] = status;
+    if (seed_out) seed_out[b] = s;
+    if (perr_out || rerr_out) {
+        double pe, re;
+        ik_eval<false>(rc, q, pd, rd, nullptr, nullptr, &pe, &re);
+        if (perr_out) perr_out[b] = pe;
+        if (rerr_out) rerr_out[b] = re;
+    }
+}
+
 }  // namespace bmpc

@@ -13,11 +13,9 @@
 #include <vector>
 
 #include "../../include/boundmpc.h"
+#include "bmpc_internal.hpp"
 
 using namespace bmpc;
-
-extern "C" void bmpc_handle_retain(bmpc_handle* h);
-extern "C" void bmpc_handle_release(bmpc_handle* h);
 
 __global__ __launch_bounds__(256) void bmpc_loop_k_bounds(int R, int N, const RobotConst* rc, double* lbx, double* ubx) {
     const int n_w = 44 * N + 6;
@@ -447,12 +445,6 @@ extern "C" int bmpc_loop_run(bmpc_loop* L, int nsteps, double* log, float* ms_to
 // finish / keep / collision-pair / prepare / start-vector kernels for just those rollouts, and the solver re-admits the
 // slot with the rollout's next problem at the start of the following super-step.  The straggler tail is then paid once per
 // run instead of once per MPC step.  Per-rollout arithmetic does not depend on the schedule: the log equals bmpc_loop_run's.
-typedef int (*bmpc_retire_hook)(void* ctx, const int* d_done, const int* d_n_done, int n_max, void* stream);
-extern "C" int bmpc_solve_dev_hooked(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx,
-                                     const double* d_p, double* d_x, double* d_f, int* d_iters, int* d_status, double* d_viol,
-                                     void* stream, bmpc_retire_hook hook, void* hook_ctx, const int* d_cont,
-                                     const int* d_prio, int prio_max);
-
 static int loop_retire_hook(void* ctx, const int* d_done, const int* d_n_done, int n_max, void* stream) {
     bmpc_loop* L = (bmpc_loop*)ctx;
     hipStream_t st = (hipStream_t)stream;

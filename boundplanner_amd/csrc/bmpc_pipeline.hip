@@ -7,6 +7,7 @@
 #define BMPC_NT 64
 #include "bmpc_pair_kernels.hpp"
 #include "bmpc_ric_kernel.hpp"
+#include "bmpc_internal.hpp"
 
 using namespace bmpc;
 

@@ -5,6 +5,7 @@
 #include "bmpc_platform_hip.hpp"
 
 #define BMPC_NT 64
+#include "bmpc_internal.hpp"
 #include "bmpc_sets.hpp"
 
 using namespace bmpc;
@@ -15,13 +16,7 @@ constexpr int SETS_NT = 64;   // one wavefront per workgroup: 64 x 32 doubles of
 __global__ void bmpc_sets_aat_kernel(int n_obs, const double* A, const int* nrows, double* AAt) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_obs * SETS_OROWS) return;
-    const int o = t / SETS_OROWS, i = t % SETS_OROWS;
-    const double* a = A + 3 * SETS_OROWS * o;
-    for (int j = 0; j < SETS_OROWS; j++) {
-        double v = 0.0;
-        if (i < nrows[o] && j < nrows[o]) v = a[3 * i] * a[3 * j] + a[3 * i + 1] * a[3 * j + 1] + a[3 * i + 2] * a[3 * j + 2];
-        AAt[SETS_OROWS * SETS_OROWS * o + SETS_OROWS * i + j] = v;
-    }
+    sets_aat_row(A, nrows, t / SETS_OROWS, t % SETS_OROWS, AAt);
 }
 
 __global__ __launch_bounds__(SETS_NT) void bmpc_sets_kernel(int B, int segment, int fixed_mid, int optimize, SetScene sc,

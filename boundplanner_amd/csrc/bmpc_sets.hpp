@@ -578,4 +578,14 @@ BMPC_INL SetResult sets_segment_lane(const SetScene& sc, const double* p0, const
     return res;
 }
 
+// row i of A A^T of obstacle o (SetScene::AAt: the segment mode's projections), zero past the obstacle's rows
+BMPC_INL void sets_aat_row(const double* A, const int* nrows, int o, int i, double* AAt) {
+    const double* a = A + 3 * SETS_OROWS * o;
+    for (int j = 0; j < SETS_OROWS; j++) {
+        double v = 0.0;
+        if (i < nrows[o] && j < nrows[o]) v = a[3 * i] * a[3 * j] + a[3 * i + 1] * a[3 * j + 1] + a[3 * i + 2] * a[3 * j + 2];
+        AAt[SETS_OROWS * SETS_OROWS * o + SETS_OROWS * i + j] = v;
+    }
+}
+
 }  // namespace bmpc

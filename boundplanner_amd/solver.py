@@ -25,6 +25,31 @@ class BmpcSetsOpts(ctypes.Structure):
 
 
 SETS_ROWS, SETS_MAXOBS, SETS_OROWS, SETS_NV = 20, 32, 15, 32       # include/boundmpc.h bmpc_convex_sets
+# Result arrays of the batched kernels, in the order of the C entries' output arguments: name -> (shape after the batch axis, dtype).
+# The numpy dicts of ik / convex_sets, the torch dicts of ik_dev / convex_sets_dev and the ctypes arguments all come from these.
+_F, _I = np.float64, np.int32
+IK_OUT = {"q": ((7,), _F), "cost": ((), _F), "pos_err": ((), _F), "rot_err": ((), _F), "iters": ((), _I), "status": ((), _I), "seed": ((), _I)}
+SETS_OUT = {"A": ((SETS_ROWS, 3), _F), "b": ((SETS_ROWS,), _F), "nrows": ((), _I), "q_ellipse": ((3, 3), _F), "centre": ((3,), _F),
+            "rounds": ((), _I), "newton": ((), _I), "collision": ((), _I), "status": ((), _I)}
+
+
+def out_arrays(table, B, alloc=np.empty):
+    """The result dict of a table for a batch of B as numpy arrays (alloc: np.empty or np.zeros)."""
+    return {k: alloc((B, *shape), dt) for k, (shape, dt) in table.items()}
+
+
+def out_tensors(table, B, device):
+    """The same as uninitialised torch tensors on `device`."""
+    import torch
+    return {k: torch.empty((B, *shape), dtype=getattr(torch, np.dtype(dt).name), device=device) for k, (shape, dt) in table.items()}
+
+
+def out_args(table, out):
+    """The output arguments of the C entry from a result dict: typed pointers of numpy arrays, device addresses of torch tensors."""
+    return [out[k].ctypes.data_as(_ip if dt is _I else _dp) if isinstance(out[k], np.ndarray) else out[k].data_ptr()
+            for k, (_, dt) in table.items()]
+
+
 SETS_STATUS = {1: "Ellipse violates constraints", 2: "the set needs more than 20 rows", 3: "no strictly interior point for the ellipsoid",
                4: "numerical failure"}
 
@@ -301,12 +326,9 @@ class HipBoundMPC:
         q0 = np.ascontiguousarray(q0, float).reshape(B, 7)
         lo = None if lo is None else np.ascontiguousarray(np.broadcast_to(np.asarray(lo, float), (B, 7)))
         hi = None if hi is None else np.ascontiguousarray(np.broadcast_to(np.asarray(hi, float), (B, 7)))
-        out = dict(q=np.empty((B, 7)), cost=np.empty(B), pos_err=np.empty(B), rot_err=np.empty(B), iters=np.empty(B, np.int32),
-                   status=np.empty(B, np.int32), seed=np.empty(B, np.int32))
+        out = out_arrays(IK_OUT, B)
         o = self._ik_opts(opts)
-        I = lambda a: a.ctypes.data_as(_ip)
-        rc = self.lib.bmpc_ik(self._h, B, int(n_seeds), ctypes.byref(o), _P(pd), _P(rd), _P(q0), _P(lo), _P(hi), _P(out["q"]),
-                              _P(out["cost"]), _P(out["pos_err"]), _P(out["rot_err"]), I(out["iters"]), I(out["status"]), I(out["seed"]))
+        rc = self.lib.bmpc_ik(self._h, B, int(n_seeds), ctypes.byref(o), _P(pd), _P(rd), _P(q0), _P(lo), _P(hi), *out_args(IK_OUT, out))
         self._chk(rc, "bmpc_ik")
         return out
 
@@ -319,16 +341,11 @@ class HipBoundMPC:
             if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
                 raise ValueError(f"ik_dev: {name} must be a contiguous float64 GPU tensor of shape {shape}")
         if out is None:
-            kw = dict(device=pd.device)
-            out = dict(q=torch.empty((B, 7), dtype=torch.float64, **kw), cost=torch.empty(B, dtype=torch.float64, **kw),
-                       pos_err=torch.empty(B, dtype=torch.float64, **kw), rot_err=torch.empty(B, dtype=torch.float64, **kw),
-                       iters=torch.empty(B, dtype=torch.int32, **kw), status=torch.empty(B, dtype=torch.int32, **kw),
-                       seed=torch.empty(B, dtype=torch.int32, **kw))
+            out = out_tensors(IK_OUT, B, pd.device)
         o = self._ik_opts(opts)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        rc = self.lib.bmpc_ik_dev(self._h, B, int(n_seeds), ctypes.byref(o), ptr(pd), ptr(rd), ptr(q0), ptr(lo), ptr(hi), ptr(out["q"]),
-                                  ptr(out["cost"]), ptr(out["pos_err"]), ptr(out["rot_err"]), ptr(out["iters"]), ptr(out["status"]),
-                                  ptr(out["seed"]), torch.cuda.current_stream(pd.device).cuda_stream or None)
+        rc = self.lib.bmpc_ik_dev(self._h, B, int(n_seeds), ctypes.byref(o), ptr(pd), ptr(rd), ptr(q0), ptr(lo), ptr(hi),
+                                  *out_args(IK_OUT, out), torch.cuda.current_stream(pd.device).cuda_stream or None)
         self._chk(rc, "bmpc_ik_dev")
         return out
 
@@ -350,15 +367,11 @@ class HipBoundMPC:
         B = p0.shape[0]
         p1 = None if p1 is None else np.ascontiguousarray(p1, float).reshape(B, 3)
         e_min, e_max = (np.ascontiguousarray(e, float).reshape(3) for e in (e_min, e_max))
-        out = dict(A=np.empty((B, SETS_ROWS, 3)), b=np.empty((B, SETS_ROWS)), nrows=np.empty(B, np.int32), q_ellipse=np.empty((B, 3, 3)),
-                   centre=np.empty((B, 3)), rounds=np.empty(B, np.int32), newton=np.empty(B, np.int32), collision=np.empty(B, np.int32),
-                   status=np.empty(B, np.int32))
+        out = out_arrays(SETS_OUT, B)
         o = self._sets_opts(p1 is not None, fixed_mid, optimize)
         I = lambda a: a.ctypes.data_as(_ip)
         rc = self.lib.bmpc_convex_sets(self._h, ctypes.byref(o), sc["n_obs"], _P(sc["A"]), _P(sc["b"]), I(sc["nrows"]), _P(sc["V"]),
-                                       I(sc["nv"]), _P(e_min), _P(e_max), B, _P(p0), _P(p1), _P(out["A"]), _P(out["b"]), I(out["nrows"]),
-                                       _P(out["q_ellipse"]), _P(out["centre"]), I(out["rounds"]), I(out["newton"]), I(out["collision"]),
-                                       I(out["status"]))
+                                       I(sc["nv"]), _P(e_min), _P(e_max), B, _P(p0), _P(p1), *out_args(SETS_OUT, out))
         self._chk(rc, "bmpc_convex_sets")
         return out
 
@@ -379,19 +392,12 @@ class HipBoundMPC:
             if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
                 raise ValueError(f"convex_sets_dev: {name} must be a contiguous {dt} GPU tensor of shape {shape}")
         if out is None:
-            kw = dict(device=p0.device)
-            out = dict(A=torch.empty((B, SETS_ROWS, 3), dtype=f64, **kw), b=torch.empty((B, SETS_ROWS), dtype=f64, **kw),
-                       nrows=torch.empty(B, dtype=i32, **kw), q_ellipse=torch.empty((B, 3, 3), dtype=f64, **kw),
-                       centre=torch.empty((B, 3), dtype=f64, **kw), rounds=torch.empty(B, dtype=i32, **kw),
-                       newton=torch.empty(B, dtype=i32, **kw), collision=torch.empty(B, dtype=i32, **kw),
-                       status=torch.empty(B, dtype=i32, **kw))
+            out = out_tensors(SETS_OUT, B, p0.device)
         o = self._sets_opts(p1 is not None, fixed_mid, optimize)
         ptr = lambda t: t.data_ptr() if t is not None else None
         rc = self.lib.bmpc_convex_sets_dev(self._h, ctypes.byref(o), int(scene["n_obs"]), ptr(scene["A"]), ptr(scene["b"]),
                                            ptr(scene["nrows"]), ptr(scene["V"]), ptr(scene["nv"]), ptr(e_min), ptr(e_max), B, ptr(p0),
-                                           ptr(p1), ptr(out["A"]), ptr(out["b"]), ptr(out["nrows"]), ptr(out["q_ellipse"]),
-                                           ptr(out["centre"]), ptr(out["rounds"]), ptr(out["newton"]), ptr(out["collision"]),
-                                           ptr(out["status"]), torch.cuda.current_stream(p0.device).cuda_stream or None)
+                                           ptr(p1), *out_args(SETS_OUT, out), torch.cuda.current_stream(p0.device).cuda_stream or None)
         self._chk(rc, "bmpc_convex_sets_dev")
         return out
 

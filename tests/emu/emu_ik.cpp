@@ -2,17 +2,10 @@
 // The identical per-lane source under the emulator's platform macros; the best seed of an instance is picked with a serial loop
 // under the same total order (ik_better) as the wavefront shuffles of bmpc_ik.hip.  Never shipped, never used by the product path.
 #include <algorithm>
-#include <cmath>
 #include <thread>
 #include <vector>
 
-#define BMPC_DEV inline
-#define BMPC_INL inline
-#define BMPC_AS1
-#define BMPC_SINCOS(x, s, c) do { (s) = std::sin(x); (c) = std::cos(x); } while (0)
-using std::fmax;
-using std::fmin;
-
+#include "emu_platform.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_ik.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_robot.hpp"
 
@@ -43,15 +36,7 @@ extern "C" int emu_ik_solve(const bmpc_robot* robot, int B, int n_seeds, const d
                 bf = f; bit = it; bst = st; bs = s;
             }
         }
-        std::copy(bq, bq + 7, q + b * 7);
-        if (cost) cost[b] = bf;
-        if (iters) iters[b] = bit;
-        if (status) status[b] = bst;
-        if (seed) seed[b] = bs;
-        double pe, re;
-        ik_eval<false>(&rc, bq, pd + b * 3, rd + b * 9, nullptr, nullptr, &pe, &re);
-        if (pos_err) pos_err[b] = pe;
-        if (rot_err) rot_err[b] = re;
+        ik_store(&rc, b, bs, bq, bf, bit, bst, pd + b * 3, rd + b * 9, q, cost, pos_err, rot_err, iters, status, seed);
     };
     const int nt = std::max(1, std::min(nthreads, B));
     std::vector<std::thread> th;

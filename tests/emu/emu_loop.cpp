@@ -2,24 +2,10 @@
 // TEST INFRASTRUCTURE ONLY: lets tests/test_device_loop.py replay the reference's closed-loop trace
 // through the identical source the HIP kernels compile, without a GPU.  Never shipped, never used by
 // the product path.
-#include <cmath>
 #include <cstring>
 #include <vector>
-#define BMPC_DEV inline
-#define BMPC_INL inline
-#define BMPC_HD inline
-#define BMPC_NOINL
-typedef double LDSD;
-#define BMPC_SYNC() do {} while (0)
-#define BMPC_LANE() 0
-#define BMPC_NT 64
-#define BMPC_BLOCK() 0
-#define BMPC_NBLOCKS() 1
-#define BMPC_AS1
-#define BMPC_SCHED_FENCE() do {} while (0)
-#define BMPC_SINCOS(x, s, c) do { (s) = std::sin(x); (c) = std::cos(x); } while (0)
-using std::fmax;
-using std::fmin;
+
+#include "emu_platform.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_loop.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_robot.hpp"
 

@@ -11,45 +11,16 @@
 #include <thread>
 #include <vector>
 
+// this build's own platform names (defined before emu_platform.hpp, which keeps them): the lanes of a workgroup are threads, so
+// the barriers and the lane index are real, the counter increment is atomic, and the Riccati kernel's trace hooks are compiled in
 static std::barrier<>* g_bar = nullptr;
 static thread_local int t_lane = 0;
 #define BMPC_EMU_TRACE 1
-#define BMPC_DEV inline
-#define BMPC_INL inline
-#define BMPC_KBODY inline
-#define BMPC_PIN(x) do {} while (0)
-#define BMPC_UNIFORM(x) (x)
-#define BMPC_OPAQUE_I(x) do {} while (0)
-#define BMPC_TOUCH_LINE(g, l) do {} while (0)
-#define BMPC_HD inline
-#define BMPC_NOINL
-typedef double LDSD;
-typedef double bmpc_v2d __attribute__((vector_size(16)));
-typedef bmpc_v2d LDSV2;
-#define BMPC_RSQRT(x) (1.0 / std::sqrt(x))
-#define BMPC_RCP(x) (1.0 / (x))
-#define BMPC_MUL24(a, b) ((a) * (b))
-#define BMPC_SCHED_FENCE() do {} while (0)
-#define BMPC_SINCOS(x, s, c) do { (s) = std::sin(x); (c) = std::cos(x); } while (0)
-#define BMPC_LDS_ADD(ptr, v) (*(ptr) += (v))
-#define BMPC_AS1
-template <int NCH, int NT> static inline void bmpc_async_copy(const double* gsrc, double* lds_dst, int lane) {
-    const int wave = lane >> 6, wl = lane & 63;
-    for (int i = 0; i < (NCH + NT / 64 - 1) / (NT / 64); i++) {
-        const int c = i * (NT / 64) + wave;
-        if (c < NCH) { lds_dst[128 * c + 2 * wl] = gsrc[128 * c + 2 * wl]; lds_dst[128 * c + 2 * wl + 1] = gsrc[128 * c + 2 * wl + 1]; }
-    }
-}
-#define BMPC_ASYNC_WAIT() do {} while (0)
 #define BMPC_SYNC() g_bar->arrive_and_wait()
 #define BMPC_FENCE_SYNC() g_bar->arrive_and_wait()
 #define BMPC_LANE() t_lane
-#define BMPC_NT 64
-#define BMPC_BLOCK() 0
-#define BMPC_NBLOCKS() 1
 #define BMPC_ATOMIC_INC(ptr) __atomic_fetch_add((ptr), 1, __ATOMIC_RELAXED)
-using std::fmax;
-using std::fmin;
+#include "emu_platform.hpp"
 
 #include "../../boundplanner_amd/csrc/bmpc_pair_kernels.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_ric_kernel.hpp"

@@ -2,26 +2,10 @@
 // The identical per-lane source under the emulator's platform macros, one CPU thread per stripe of instances.  Never shipped, never
 // used by the product path.
 #include <algorithm>
-#include <cmath>
 #include <thread>
 #include <vector>
 
-#define BMPC_DEV inline
-#define BMPC_INL inline
-#define BMPC_HD inline
-#define BMPC_NOINL
-typedef double LDSD;
-#define BMPC_SYNC() do {} while (0)
-#define BMPC_LANE() 0
-#define BMPC_NT 64
-#define BMPC_BLOCK() 0
-#define BMPC_NBLOCKS() 1
-#define BMPC_AS1
-#define BMPC_SCHED_FENCE() do {} while (0)
-#define BMPC_SINCOS(x, s, c) do { (s) = std::sin(x); (c) = std::cos(x); } while (0)
-using std::fmax;
-using std::fmin;
-
+#include "emu_platform.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_sets.hpp"
 
 using namespace bmpc;
@@ -36,12 +20,7 @@ extern "C" int emu_convex_sets(int n_obs, const double* obs_A, const double* obs
         if (obs_nrows[o] < 0 || obs_nrows[o] > SETS_OROWS || obs_nv[o] < 1 || obs_nv[o] > SETS_NV) return 1;
     std::vector<double> AAt((size_t)std::max(n_obs, 1) * SETS_OROWS * SETS_OROWS, 0.0);
     for (int o = 0; o < n_obs; o++)
-        for (int i = 0; i < obs_nrows[o]; i++)
-            for (int j = 0; j < obs_nrows[o]; j++) {
-                const double* a = obs_A + 3 * SETS_OROWS * o;
-                AAt[SETS_OROWS * SETS_OROWS * o + SETS_OROWS * i + j] =
-                    a[3 * i] * a[3 * j] + a[3 * i + 1] * a[3 * j + 1] + a[3 * i + 2] * a[3 * j + 2];
-            }
+        for (int i = 0; i < SETS_OROWS; i++) sets_aat_row(obs_A, obs_nrows, o, i, AAt.data());
     SetScene sc{n_obs, obs_A, obs_b, obs_nrows, obs_V, obs_nv, AAt.data(), {e_min[0], e_min[1], e_min[2]}, {e_max[0], e_max[1], e_max[2]}};
     auto one = [&](long t) {
         double dist[SETS_MAXOBS];

@@ -1,13 +1,10 @@
 """ctypes access to the CPU build of the closed-loop step logic (tests/emu/emu_loop.cpp) -- TEST INFRASTRUCTURE ONLY."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "emu", "emu_loop.cpp")
-LIB = os.path.join(ROOT, "tests", "emu", "libbmpc_emuloop.so")
+import emu_build
+
 _dp = ctypes.POINTER(ctypes.c_double)
 P = lambda a: a.ctypes.data_as(_dp) if a is not None else None
 _lib = None
@@ -16,11 +13,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        cs = os.path.join(ROOT, "boundplanner_amd", "csrc")
-        deps = [SRC] + [os.path.join(cs, f) for f in ("bmpc_loop.hpp", "bmpc_device.hpp", "bmpc_robot.hpp")]
-        if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-            subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", LIB, SRC])
-        _lib = ctypes.CDLL(LIB)
+        _lib = ctypes.CDLL(emu_build.build("emu_loop.cpp", "libbmpc_emuloop.so", ("-O1", "-g")))
     return _lib
 
 

@@ -1,25 +1,18 @@
 """ctypes access to the CPU thread emulation of the batch-synchronous HIP pipeline (tests/emu/emu_pipe.cpp)
 -- debugging aid, TEST INFRASTRUCTURE ONLY."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "emu", "emu_pipe.cpp")
-LIB = os.path.join(ROOT, "tests", "emu", "libbmpc_emupipe.so")
+import emu_build
+
+LIB = "libbmpc_emupipe.so"
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
 
 
 def build(force=False, lib=LIB, defs=()):
-    cs = os.path.join(ROOT, "boundplanner_amd", "csrc")
-    deps = [SRC] + [os.path.join(cs, f) for f in os.listdir(cs) if f.endswith(".hpp")]
-    if force or not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", *defs,
-                               "-o", lib, SRC])
-    return lib
+    return emu_build.build("emu_pipe.cpp", lib, ("-O1", "-g", *defs), force=force)
 
 
 # build variants of the device source (kept behind build knobs; the product build uses the defaults)

@@ -2,14 +2,11 @@
 Same arguments and results as HipBoundMPC.convex_sets; `sets` is a sets_fn for ConvexSetFinder / BoundPlanner.  Never imported by the
 product package."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "emu", "emu_sets.cpp")
-LIB = os.path.join(ROOT, "tests", "emu", "libbmpc_emusets.so")
+import emu_build
+
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
 _lib = None
@@ -18,31 +15,23 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        cs = os.path.join(ROOT, "boundplanner_amd", "csrc")
-        deps = [SRC] + [os.path.join(cs, f) for f in ("bmpc_sets.hpp", "bmpc_loop.hpp", "bmpc_device.hpp")]
-        if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-            subprocess.check_call(["g++", "-std=c++20", "-O2", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", "-o", LIB, SRC])
-        _lib = ctypes.CDLL(LIB)
+        _lib = ctypes.CDLL(emu_build.build("emu_sets.cpp", "libbmpc_emusets.so", ("-O2",)))
     return _lib
 
 
 def sets(obs_sets, obs_points_sets, e_min, e_max, p0, p1=None, fixed_mid=False, optimize=True, nthreads=8):
     """The dict of HipBoundMPC.convex_sets, computed on the CPU."""
-    from boundplanner_amd.solver import pack_set_scene
+    from boundplanner_amd.solver import SETS_OUT, out_args, out_arrays, pack_set_scene
     sc = pack_set_scene(obs_sets, obs_points_sets)
     p0 = np.ascontiguousarray(p0, float).reshape(-1, 3)
     B = p0.shape[0]
     p1 = None if p1 is None else np.ascontiguousarray(p1, float).reshape(B, 3)
     e_min, e_max = (np.ascontiguousarray(e, float).reshape(3) for e in (e_min, e_max))
-    out = dict(A=np.zeros((B, 20, 3)), b=np.zeros((B, 20)), nrows=np.zeros(B, np.int32), q_ellipse=np.zeros((B, 3, 3)),
-               centre=np.zeros((B, 3)), rounds=np.zeros(B, np.int32), newton=np.zeros(B, np.int32), collision=np.zeros(B, np.int32),
-               status=np.zeros(B, np.int32))
+    out = out_arrays(SETS_OUT, B, np.zeros)
     P = lambda a: a.ctypes.data_as(_dp) if a is not None else None
     I = lambda a: a.ctypes.data_as(_ip)
     rc = lib().emu_convex_sets(sc["n_obs"], P(sc["A"]), P(sc["b"]), I(sc["nrows"]), P(sc["V"]), I(sc["nv"]), P(e_min), P(e_max), B,
-                               P(p0), P(p1), int(bool(fixed_mid)), int(bool(optimize)), P(out["A"]), P(out["b"]), I(out["nrows"]),
-                               P(out["q_ellipse"]), P(out["centre"]), I(out["rounds"]), I(out["newton"]), I(out["collision"]),
-                               I(out["status"]), int(nthreads))
+                               P(p0), P(p1), int(bool(fixed_mid)), int(bool(optimize)), *out_args(SETS_OUT, out), int(nthreads))
     if rc != 0:
         raise ValueError(f"emu_convex_sets: invalid arguments ({rc})")
     return out
