@@ -9,6 +9,7 @@
 #include "bmpc_robot.hpp"
 
 #include <chrono>
+#include <climits>
 #include <string>
 #include <vector>
 
@@ -24,8 +25,6 @@ __global__ __launch_bounds__(256) void bmpc_loop_k_bounds(int R, int N, const Ro
     loop_bound_const(rc, N, (int)(e % n_w), lbx + e, ubx + e);
 }
 
-// closest pairs collision-point segment <-> obstacle: one thread per (rollout, collision point), blockIdx.y = obstacle, so
-// that the obstacle's rows are wave-uniform (scalar loads)
 // Every kernel below runs either over all R rollouts (list == nullptr) or over the rollouts of a device list of length
 // *n_list (bmpc_loop_run_async: the rollouts whose solve has just retired).
 #define LOOP_ROLLOUT(e, r)                                  \
@@ -33,6 +32,8 @@ __global__ __launch_bounds__(256) void bmpc_loop_k_bounds(int R, int N, const Ro
     if (list) { if ((e) >= *n_list) return; r = list[e]; }  \
     else if ((e) >= R) return;
 
+// closest pairs collision-point segment <-> obstacle of the shared scene (bmpc_loop_set_obstacles): one thread per (rollout, collision
+// point), blockIdx.y = obstacle, so that the obstacle's rows are wave-uniform (scalar loads)
 __global__ __launch_bounds__(64) void bmpc_loop_k_colpairs(int R, const RobotConst* rc, LoopScene sc, const double* S, double* colres,
                                                            const int* list, const int* n_list) {
     const int e6 = blockIdx.x * 64 + threadIdx.x, ob = blockIdx.y;
@@ -43,16 +44,46 @@ __global__ __launch_bounds__(64) void bmpc_loop_k_colpairs(int R, const RobotCon
     loop_collision_pair(rc, sc, s, pt, ob, colres + (((size_t)r * 6 + pt) * sc.n_obs + ob) * LP_CRES);
 }
 
+// the prepare phase of rollout r in the scene sc, res: the closest-pair results of the rollout (both prepare kernels)
+static __device__ __forceinline__ void prepare_rollout(int r, int N, const RobotConst* rc, double* S, const double* prev, double* p,
+                                                       double* lbx, double* ubx, const LoopScene& sc, const double* res) {
+    const size_t n_w = 44 * N + 6;
+    double* s = S + (size_t)r * LS_SIZE;
+    if (s[LS_dead] != 0.0) return;
+    loop_prepare(rc, N, s, prev + r * n_w, p + (size_t)r * NPAR, lbx + r * n_w, ubx + r * n_w, &sc, res);
+}
+
 __global__ __launch_bounds__(64) void bmpc_loop_k_prepare(int R, int N, const RobotConst* rc, double* S, const double* prev,
                                                           double* p, double* lbx, double* ubx, LoopScene sc, const double* colres,
                                                           const int* list, const int* n_list) {
     const int e = blockIdx.x * 64 + threadIdx.x;
     LOOP_ROLLOUT(e, r)
-    const size_t n_w = 44 * N + 6;
-    double* s = S + (size_t)r * LS_SIZE;
+    prepare_rollout(r, N, rc, S, prev, p, lbx, ubx, sc, colres ? colres + (size_t)r * 6 * sc.n_obs * LP_CRES : nullptr);
+}
+
+// The same two kernels with one scene per rollout (bmpc_loop_set_scenes).  The rollouts of a wavefront look at different scenes -- and
+// bmpc_loop_run_async hands over an arbitrary list of rollouts -- so nothing about the obstacle is wave-uniform here: every lane
+// resolves (rollout, collision point, obstacle slot = blockIdx.y) -> scene -> obstacle itself and reads the obstacle's rows with its
+// own (vector) loads; a lane whose scene has no obstacle in this slot has nothing to do.  The arithmetic is the shared source
+// (loop_collision_pair, loop_prepare), so an obstacle gives bitwise the numbers it gives through bmpc_loop_k_colpairs.
+__global__ __launch_bounds__(64) void bmpc_loop_k_colpairs_scenes(int R, const RobotConst* rc, LoopSceneTable tab, const double* S,
+                                                                  double* colres, const int* list, const int* n_list) {
+    const int e6 = blockIdx.x * 64 + threadIdx.x, ob = blockIdx.y;
+    const int e = e6 / 6, pt = e6 - 6 * e;
+    LOOP_ROLLOUT(e, r)
+    const LoopScene sc = loop_scene_of(tab, r);
+    if (ob >= sc.n_obs) return;
+    const double* s = S + (size_t)r * LS_SIZE;
     if (s[LS_dead] != 0.0) return;
-    loop_prepare(rc, N, s, prev + r * n_w, p + (size_t)r * NPAR, lbx + r * n_w, ubx + r * n_w, &sc,
-                 colres ? colres + (size_t)r * 6 * sc.n_obs * LP_CRES : nullptr);
+    loop_collision_pair(rc, sc, s, pt, ob, colres + loop_colres_of(tab, r) + (size_t)(pt * sc.n_obs + ob) * LP_CRES);
+}
+
+__global__ __launch_bounds__(64) void bmpc_loop_k_prepare_scenes(int R, int N, const RobotConst* rc, double* S, const double* prev,
+                                                                 double* p, double* lbx, double* ubx, LoopSceneTable tab,
+                                                                 const double* colres, const int* list, const int* n_list) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    LOOP_ROLLOUT(e, r)
+    prepare_rollout(r, N, rc, S, prev, p, lbx, ubx, loop_scene_of(tab, r), colres + loop_colres_of(tab, r));
 }
 
 __global__ __launch_bounds__(256) void bmpc_loop_k_x0(int R, int N, const double* S, const double* prev, double* x0,
@@ -141,6 +172,8 @@ struct bmpc_loop {
     double* d_scene = nullptr;     // A | b | AAt | V
     int* d_scene_i = nullptr;      // nrows | nv
     double* d_colres = nullptr;
+    LoopSceneTable tab{};          // bmpc_loop_set_scenes: one scene per rollout (n_scenes > 0); its obstacles live in d_scene / d_scene_i too
+    int *d_first = nullptr, *d_rollout_scene = nullptr;
     int *d_steps_left = nullptr, *d_cont = nullptr;    // bmpc_loop_run_async
     int* d_prio = nullptr;         // ... its fast lane: [R] 1 = the rollout lags behind (bmpc_loop_k_prio)
     int prio_max = 0;
@@ -214,6 +247,8 @@ extern "C" void bmpc_loop_destroy(bmpc_loop* L) {
     if (L->d_scene) (void)hipFree(L->d_scene);
     if (L->d_scene_i) (void)hipFree(L->d_scene_i);
     if (L->d_colres) (void)hipFree(L->d_colres);
+    if (L->d_first) (void)hipFree(L->d_first);
+    if (L->d_rollout_scene) (void)hipFree(L->d_rollout_scene);
     if (L->d_steps_left) (void)hipFree(L->d_steps_left);
     if (L->d_cont) (void)hipFree(L->d_cont);
     if (L->d_prio) (void)hipFree(L->d_prio);
@@ -287,59 +322,109 @@ extern "C" int bmpc_loop_download(bmpc_loop* L, int first, int count, double* st
     return 0;
 }
 
+// forget the installed obstacles, shared scene or table (the loop's stream is idle)
+static void drop_obstacles(bmpc_loop* L) {
+    void* bufs[] = {L->d_scene, L->d_scene_i, L->d_colres, L->d_first, L->d_rollout_scene};
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    L->d_scene = nullptr; L->d_scene_i = nullptr; L->d_colres = nullptr; L->d_first = nullptr; L->d_rollout_scene = nullptr;
+    L->sc = LoopScene{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    L->tab = LoopSceneTable{};
+}
+
+static bool obstacles_ok(bmpc_loop* L, size_t n, const int* nrows, const int* nv) {
+    for (size_t i = 0; i < n; i++)
+        if (nrows[i] < 1 || nrows[i] > LP_ROWS || nv[i] < 1 || nv[i] > LP_NV) { L->err = "obstacle with too many rows or vertices"; return false; }
+    return true;
+}
+
+// n > 0 obstacles (one scene, or all scenes of a table back to back) -> d_scene / d_scene_i, the closest-pair results for `stride`
+// obstacles per rollout -> d_colres; `all`: the LoopScene over the n obstacles
+static int install_obstacles(bmpc_loop* L, size_t n, const double* A, const double* b, const int* nrows, const double* V, const int* nv,
+                             int stride, LoopScene* all) {
+    std::vector<double> h(n * LP_OBS_DOUBLES);
+    std::vector<int> hi(n * LP_OBS_INTS);
+    loop_pack_obstacles(n, A, b, nrows, V, nv, h.data(), hi.data());
+    LCHK(L, hipMalloc((void**)&L->d_scene, h.size() * sizeof(double)));
+    LCHK(L, hipMemcpy(L->d_scene, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    LCHK(L, hipMalloc((void**)&L->d_scene_i, hi.size() * sizeof(int)));
+    LCHK(L, hipMemcpy(L->d_scene_i, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
+    LCHK(L, hipMalloc((void**)&L->d_colres, (size_t)L->R * 6 * stride * LP_CRES * sizeof(double)));
+    LCHK(L, hipMemset(L->d_colres, 0, (size_t)L->R * 6 * stride * LP_CRES * sizeof(double)));
+    *all = loop_scene_over(n, L->d_scene, L->d_scene_i);
+    return 0;
+}
+
 extern "C" int bmpc_loop_set_obstacles(bmpc_loop* L, int n_obs, const double* A, const double* b, const int* nrows, const double* V,
                                        const int* nv) {
     if (!L || n_obs < 0 || n_obs > LP_MAXOBS || (n_obs > 0 && (!A || !b || !nrows || !V || !nv))) { if (L) L->err = "bmpc_loop_set_obstacles: bad arguments"; return 1; }
     LCHK(L, hipSetDevice(L->dev));
     LCHK(L, hipStreamSynchronize(L->st));
-    if (L->d_scene) { (void)hipFree(L->d_scene); L->d_scene = nullptr; }
-    if (L->d_scene_i) { (void)hipFree(L->d_scene_i); L->d_scene_i = nullptr; }
-    if (L->d_colres) { (void)hipFree(L->d_colres); L->d_colres = nullptr; }
-    L->sc = LoopScene{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    drop_obstacles(L);
     if (n_obs == 0) return 0;
-    for (int i = 0; i < n_obs; i++)
-        if (nrows[i] < 1 || nrows[i] > LP_ROWS || nv[i] < 1 || nv[i] > LP_NV) { L->err = "obstacle with too many rows or vertices"; return 1; }
-    const size_t nA = (size_t)n_obs * 45, nb = (size_t)n_obs * LP_ROWS, nAAt = (size_t)n_obs * LP_ROWS * LP_ROWS, nV = (size_t)n_obs * LP_NV * 3;
-    const size_t nBox = (size_t)n_obs * 6;
-    std::vector<double> h(nA + nb + nAAt + nV + nBox, 0.0);
-    std::vector<int> hi(3 * (size_t)n_obs);
-    for (int o = 0; o < n_obs; o++) {
-        for (int r = 0; r < nrows[o]; r++) {
-            for (int c = 0; c < 3; c++) h[45 * o + 3 * r + c] = A[45 * o + 3 * r + c];
-            h[nA + LP_ROWS * o + r] = b[LP_ROWS * o + r];
-        }
-        for (int r = 0; r < nrows[o]; r++)
-            for (int q = 0; q < nrows[o]; q++) {
-                double sum = 0;
-                for (int c = 0; c < 3; c++) sum += A[45 * o + 3 * r + c] * A[45 * o + 3 * q + c];
-                h[nA + nb + (size_t)LP_ROWS * LP_ROWS * o + LP_ROWS * r + q] = sum;
-            }
-        for (int v = 0; v < nv[o]; v++)
-            for (int c = 0; c < 3; c++) h[nA + nb + nAAt + 3 * ((size_t)LP_NV * o + v) + c] = V[3 * (LP_NV * o + v) + c];
-        hi[o] = nrows[o]; hi[n_obs + o] = nv[o];
-        double* bx = h.data() + nA + nb + nAAt + nV + 6 * (size_t)o;
-        hi[2 * n_obs + o] = loop_detect_box(A + 45 * o, b + LP_ROWS * o, nrows[o], bx, bx + 3) ? 1 : 0;
+    if (!obstacles_ok(L, (size_t)n_obs, nrows, nv)) return 1;
+    return install_obstacles(L, (size_t)n_obs, A, b, nrows, V, nv, n_obs, &L->sc);
+}
+
+extern "C" int bmpc_loop_set_scenes(bmpc_loop* L, int n_scenes, const int* n_obs, const double* A, const double* b, const int* nrows,
+                                    const double* V, const int* nv) {
+    if (!L) return 1;
+    if (n_scenes < 0 || (n_scenes > 0 && !n_obs)) { L->err = "bmpc_loop_set_scenes: bad arguments"; return 1; }
+    std::vector<int> first((size_t)n_scenes + 1, 0);
+    int max_obs = 0;
+    for (int s = 0; s < n_scenes; s++) {
+        if (n_obs[s] < 0 || n_obs[s] > LP_MAXOBS) { L->err = "bmpc_loop_set_scenes: a scene has more than 16 obstacles (or fewer than 0)"; return 1; }
+        if (first[s] > INT_MAX - LP_MAXOBS) { L->err = "bmpc_loop_set_scenes: too many obstacles"; return 1; }
+        first[s + 1] = first[s] + n_obs[s];
+        if (n_obs[s] > max_obs) max_obs = n_obs[s];
     }
-    LCHK(L, hipMalloc((void**)&L->d_scene, h.size() * sizeof(double)));
-    LCHK(L, hipMemcpy(L->d_scene, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    LCHK(L, hipMalloc((void**)&L->d_scene_i, hi.size() * sizeof(int)));
-    LCHK(L, hipMemcpy(L->d_scene_i, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice));
-    LCHK(L, hipMalloc((void**)&L->d_colres, (size_t)L->R * 6 * n_obs * LP_CRES * sizeof(double)));
-    LCHK(L, hipMemset(L->d_colres, 0, (size_t)L->R * 6 * n_obs * LP_CRES * sizeof(double)));
-    L->sc = LoopScene{n_obs, L->d_scene, L->d_scene + nA, L->d_scene + nA + nb, L->d_scene_i, L->d_scene + nA + nb + nAAt, L->d_scene_i + n_obs,
-                      L->d_scene + nA + nb + nAAt + nV, L->d_scene_i + 2 * n_obs};
+    const size_t total = (size_t)first[n_scenes];
+    if (total > 0 && (!A || !b || !nrows || !V || !nv)) { L->err = "bmpc_loop_set_scenes: bad arguments"; return 1; }
+    if (!obstacles_ok(L, total, nrows, nv)) return 1;
+    LCHK(L, hipSetDevice(L->dev));
+    LCHK(L, hipStreamSynchronize(L->st));
+    drop_obstacles(L);
+    if (n_scenes == 0) return 0;
+    LoopSceneTable tab{};
+    if (total > 0) { if (int rc = install_obstacles(L, total, A, b, nrows, V, nv, max_obs, &tab.all)) return rc; }
+    const std::vector<int> none((size_t)L->R, -1);
+    LCHK(L, hipMalloc((void**)&L->d_first, first.size() * sizeof(int)));
+    LCHK(L, hipMemcpy(L->d_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+    LCHK(L, hipMalloc((void**)&L->d_rollout_scene, none.size() * sizeof(int)));
+    LCHK(L, hipMemcpy(L->d_rollout_scene, none.data(), none.size() * sizeof(int), hipMemcpyHostToDevice));
+    tab.first = L->d_first; tab.scene = L->d_rollout_scene; tab.n_scenes = n_scenes; tab.max_obs = max_obs;
+    L->tab = tab;
+    return 0;
+}
+
+extern "C" int bmpc_loop_set_rollout_scenes(bmpc_loop* L, int first, int count, const int* scene) {
+    if (!range_ok(L, first, count)) return 1;
+    if (!scene) { L->err = "bmpc_loop_set_rollout_scenes: bad arguments"; return 1; }
+    for (int i = 0; i < count; i++)
+        if (scene[i] < -1 || scene[i] >= L->tab.n_scenes) { L->err = "bmpc_loop_set_rollout_scenes: scene index out of range"; return 1; }
+    if (L->tab.n_scenes == 0) return 0;       // no table: every rollout is at -1 already (or on the shared scene of bmpc_loop_set_obstacles)
+    LCHK(L, hipSetDevice(L->dev));
+    LCHK(L, hipStreamSynchronize(L->st));
+    LCHK(L, hipMemcpy(L->d_rollout_scene + first, scene, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
     return 0;
 }
 
 // n rollouts at most: all of them (list == nullptr, n == R) or those of a device list
 static int launch_prepare(bmpc_loop* L, hipStream_t st, int n, const int* list = nullptr, const int* n_list = nullptr) {
     const size_t ne = (size_t)n * L->n_w;
-    if (L->sc.n_obs > 0) {
-        hipLaunchKernelGGL(bmpc_loop_k_colpairs, dim3((n * 6 + 63) / 64, L->sc.n_obs), dim3(64), 0, st, L->R, L->d_rc, L->sc, L->d_S,
-                           L->d_colres, list, n_list);
+    if (L->tab.n_scenes > 0) {             // one scene per rollout
+        if (L->tab.max_obs > 0)
+            hipLaunchKernelGGL(bmpc_loop_k_colpairs_scenes, dim3((n * 6 + 63) / 64, L->tab.max_obs), dim3(64), 0, st, L->R, L->d_rc, L->tab,
+                               L->d_S, L->d_colres, list, n_list);
+        hipLaunchKernelGGL(bmpc_loop_k_prepare_scenes, dim3((n + 63) / 64), dim3(64), 0, st, L->R, L->N, L->d_rc, L->d_S, L->d_prev,
+                           L->d_p, L->d_lbx, L->d_ubx, L->tab, L->d_colres, list, n_list);
+    } else {
+        if (L->sc.n_obs > 0) {
+            hipLaunchKernelGGL(bmpc_loop_k_colpairs, dim3((n * 6 + 63) / 64, L->sc.n_obs), dim3(64), 0, st, L->R, L->d_rc, L->sc, L->d_S,
+                               L->d_colres, list, n_list);
+        }
+        hipLaunchKernelGGL(bmpc_loop_k_prepare, dim3((n + 63) / 64), dim3(64), 0, st, L->R, L->N, L->d_rc, L->d_S, L->d_prev,
+                           L->d_p, L->d_lbx, L->d_ubx, L->sc, L->d_colres, list, n_list);
     }
-    hipLaunchKernelGGL(bmpc_loop_k_prepare, dim3((n + 63) / 64), dim3(64), 0, st, L->R, L->N, L->d_rc, L->d_S, L->d_prev,
-                       L->d_p, L->d_lbx, L->d_ubx, L->sc, L->d_colres, list, n_list);
     hipLaunchKernelGGL(bmpc_loop_k_x0, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, L->R, L->N, L->d_S, L->d_prev, L->d_x0,
                        list, n_list);
     LCHK(L, hipGetLastError());

@@ -246,8 +246,8 @@ BMPC_INL void lp_path_update(double* S, bool sw) {
 }
 
 // ---- per-step collision sets with obstacles (ConvexSetFinder.find_set_collision_avoidance, ---------
-// ConvexSetFinder.py:309-375, with compute_set_projs_line :491-510): the scene's obstacle polytopes are shared
-// by all rollouts.  The closest pair between the segment [p(q0), p(qf)] of a collision point and a polytope is the
+// ConvexSetFinder.py:309-375, with compute_set_projs_line :491-510): the obstacle polytopes of a scene, one scene for all
+// rollouts (bmpc_loop_set_obstacles) or one per rollout out of a table (bmpc_loop_set_scenes).  The closest pair between the segment [p(q0), p(qf)] of a collision point and a polytope is the
 // algorithm of the host restatement (boundplanner_amd/collision_sets.py: golden section over the segment
 // parameter, each distance an exact projection by Hildreth's dual coordinate ascent), so that both sides agree
 // to rounding; one thread per (rollout, collision point, obstacle), then the greedy nearest-first selection of
@@ -287,6 +287,60 @@ inline bool loop_detect_box(const double* A, const double* b, int nr, double* lo
     for (int i = 0; i < 6; i++) if (!have[i]) return false;
     return true;
 }
+
+// host side: the device image of n obstacles given in the layout of bmpc_loop_set_obstacles (A [n][15][3], b [n][15], nrows, V [n][32][3],
+// nv) -- hd: A | b | AAt | V | box ([n][45], [n][15], [n][15][15], [n][32][3], [n][6]), hi: nrows | nv | is_box; rows and vertices beyond
+// nrows / nv are zero.  Both bmpc_loop_set_obstacles and bmpc_loop_set_scenes (all scenes' obstacles back to back) upload this image, so
+// that A A^T, which Hildreth's iteration reads, is rounded by the same host code whichever entry installed the obstacle.
+constexpr int LP_OBS_DOUBLES = 45 + LP_ROWS + LP_ROWS * LP_ROWS + 3 * LP_NV + 6, LP_OBS_INTS = 3;
+inline void loop_pack_obstacles(size_t n, const double* A, const double* b, const int* nrows, const double* V, const int* nv, double* hd, int* hi) {
+    const size_t nA = n * 45, nb = n * LP_ROWS, nAAt = n * LP_ROWS * LP_ROWS, nV = n * LP_NV * 3;
+    for (size_t i = 0; i < n * LP_OBS_DOUBLES; i++) hd[i] = 0.0;
+    for (size_t o = 0; o < n; o++) {
+        for (int r = 0; r < nrows[o]; r++) {
+            for (int c = 0; c < 3; c++) hd[45 * o + 3 * r + c] = A[45 * o + 3 * r + c];
+            hd[nA + LP_ROWS * o + r] = b[LP_ROWS * o + r];
+        }
+        for (int r = 0; r < nrows[o]; r++)
+            for (int q = 0; q < nrows[o]; q++) {
+                double sum = 0;
+                for (int c = 0; c < 3; c++) sum += A[45 * o + 3 * r + c] * A[45 * o + 3 * q + c];
+                hd[nA + nb + (size_t)LP_ROWS * LP_ROWS * o + LP_ROWS * r + q] = sum;
+            }
+        for (int v = 0; v < nv[o]; v++)
+            for (int c = 0; c < 3; c++) hd[nA + nb + nAAt + 3 * ((size_t)LP_NV * o + v) + c] = V[3 * (LP_NV * o + v) + c];
+        hi[o] = nrows[o]; hi[n + o] = nv[o];
+        double* bx = hd + nA + nb + nAAt + nV + 6 * o;
+        hi[2 * n + o] = loop_detect_box(A + 45 * o, b + LP_ROWS * o, nrows[o], bx, bx + 3) ? 1 : 0;
+    }
+}
+// the LoopScene over such an image at base addresses hd / hi (host or device)
+inline LoopScene loop_scene_over(size_t n, const double* hd, const int* hi) {
+    const size_t nA = n * 45, nb = n * LP_ROWS, nAAt = n * LP_ROWS * LP_ROWS, nV = n * LP_NV * 3;
+    return LoopScene{(int)n, hd, hd + nA, hd + nA + nb, hi, hd + nA + nb + nAAt, hi + n, hd + nA + nb + nAAt + nV, hi + 2 * n};
+}
+
+// ---- one scene per rollout (bmpc_loop_set_scenes) ----------------------------------------------------
+// The obstacles of all scenes lie back to back in `all` (only the obstacles that exist); scene s owns obstacles first[s] ..
+// first[s + 1] - 1.  Which scene a rollout looks at is configuration of the loop, not rollout state: scene[r], -1 = no obstacles.
+struct LoopSceneTable {
+    LoopScene all;        // n_obs = first[n_scenes]
+    const int* first;     // [n_scenes + 1]
+    const int* scene;     // [R]
+    int n_scenes, max_obs;      // max_obs: the largest obstacle count of a scene = the stride of the closest-pair results
+};
+
+// the scene rollout r looks at, as the LoopScene the shared-scene code takes (n_obs = 0: obstacle-free collision sets)
+BMPC_INL LoopScene loop_scene_of(const LoopSceneTable& t, int r) {
+    const int s = t.scene[r];
+    if (s < 0) return LoopScene{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t o = (size_t)t.first[s];
+    return LoopScene{t.first[s + 1] - (int)o, t.all.A + 45 * o, t.all.b + LP_ROWS * o, t.all.AAt + LP_ROWS * LP_ROWS * o, t.all.nrows + o,
+                     t.all.V + 3 * LP_NV * o, t.all.nv + o, t.all.box + 6 * o, t.all.is_box + o};
+}
+// where the closest-pair results of rollout r start: blocks of the table's largest obstacle count, filled densely
+// ([point][obstacle of the rollout's own scene], the layout loop_prepare reads)
+BMPC_INL size_t loop_colres_of(const LoopSceneTable& t, int r) { return (size_t)r * 6 * t.max_obs * LP_CRES; }
 
 // Euclidean projection of y onto {x: A x <= b - 0.001} (collision_sets._project_polytope).  Loops run over the fixed
 // LP_ROWS with an early exit at nr so that, unrolled, Ay / lam stay in registers (static indices)

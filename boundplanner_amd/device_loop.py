@@ -8,8 +8,9 @@ boundplanner_amd/csrc/bmpc_loop.hpp, and the HIP kernels carry on from there
 (BoundMPC.step / compute_return_data / MPCNode.step, BoundMPC.py:388-1040, MPCNode.py:106-160).
 
 No CPU fallback: `DeviceLoop` needs libboundmpc_hip.so and a GPU.  Scene obstacles (polytopes with their vertices, the
-inputs of ConvexSetFinder.find_set_collision_avoidance, ConvexSetFinder.py:309-375) are shared by all rollouts of a loop:
-`set_obstacles`; the per-step collision sets are then computed on the device as well.
+inputs of ConvexSetFinder.find_set_collision_avoidance, ConvexSetFinder.py:309-375) are either one scene that all rollouts of
+a loop use (`set_obstacles`) or a table of scenes of which every rollout names its own (`set_scenes`, `set_rollout_scene`); the
+per-step collision sets are then computed on the device as well.
 """
 import ctypes
 
@@ -160,6 +161,27 @@ class DeviceLoop:
         A, b, nrows, V, nv = pack_obstacles(obs_sets, obs_points_sets)
         self._chk(self.lib.bmpc_loop_set_obstacles(self._l, len(obs_sets), self._P(A), self._P(b), nrows.ctypes.data_as(_ip),
                                                    self._P(V), nv.ctypes.data_as(_ip)), "bmpc_loop_set_obstacles")
+
+    def set_scenes(self, scenes, rollout_scene=None):
+        """One scene per rollout: `scenes` is a list of (obs_sets, obs_points_sets) pairs as set_obstacles takes them (an empty pair
+        is a scene without obstacles, at most 16 obstacles per scene), `rollout_scene` the scene index of every rollout (length R,
+        -1 = no obstacles; default: all -1).  Replaces the table or the shared scene installed before.  The assignment is
+        configuration of the loop: download() / upload() and the records do not carry it."""
+        if rollout_scene is not None and len(rollout_scene) != self.R:
+            raise ValueError(f"rollout_scene needs one entry per rollout ({self.R})")
+        packed = [pack_obstacles(sets, pts) for sets, pts in scenes]
+        n_obs = np.array([len(p[2]) for p in packed], np.int32)
+        A, b, nrows, V, nv = (np.ascontiguousarray(np.concatenate([p[i] for p in packed])) if packed else np.zeros(0, t)
+                              for i, t in enumerate((float, float, np.int32, float, np.int32)))
+        self._chk(self.lib.bmpc_loop_set_scenes(self._l, len(packed), n_obs.ctypes.data_as(_ip), self._P(A), self._P(b), nrows.ctypes.data_as(_ip),
+                                                self._P(V), nv.ctypes.data_as(_ip)), "bmpc_loop_set_scenes")
+        if rollout_scene is not None:
+            self.set_rollout_scene(0, rollout_scene)
+
+    def set_rollout_scene(self, r, scene):
+        """Rollout r looks at scene `scene` of the table from now on (-1: no obstacles); with an array, rollouts r, r + 1, ..."""
+        sc = np.ascontiguousarray(np.atleast_1d(scene), np.int32)
+        self._chk(self.lib.bmpc_loop_set_rollout_scenes(self._l, int(r), len(sc), sc.ctypes.data_as(_ip)), "bmpc_loop_set_rollout_scenes")
 
     def upload(self, first=0, count=None):
         count = self.R - first if count is None else count

@@ -170,3 +170,26 @@ def boxes_to_sets(boxes):
         sets.append([np.vstack((np.eye(3), -np.eye(3))), np.concatenate((hi, -lo))])
         pts.append(np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])]))
     return sets, pts
+
+
+def random_box_scenes(seed, k, n_obs, keep_clear, lo=(-0.3, -0.9, 0.0), hi=(0.9, 0.5, 1.1), gap=(0.12, 0.5)):
+    """k scenes of n_obs axis-aligned boxes each (half sizes 0.03 .. 0.15 m, [xmin, ymin, zmin, xmax, ymax, zmax]) near the arm's
+    sweep: every box lies between gap[0] and gap[1] from the nearest of the points `keep_clear` [m][3] (collision points of the start
+    configurations, the goal), so that no collision point starts inside an obstacle.  One PCG64 stream, scene after scene: the
+    first scenes of a larger table are the scenes of a smaller one.  ValueError when a scene cannot be filled (no admissible
+    box among 4000 candidates per missing box)."""
+    rng = np.random.default_rng(seed)
+    pts = np.asarray(keep_clear, float).reshape(-1, 3)
+    out = np.zeros((k, n_obs, 6))
+    for s in range(k):
+        n = tries = 0
+        while n < n_obs:
+            tries += 1
+            if tries > 1000:
+                raise ValueError(f"random_box_scenes: scene {s}: no box between {gap[0]} and {gap[1]} m from the points to keep clear")
+            c = rng.uniform(lo, hi, size=(4 * n_obs, 3)); h = rng.uniform(0.03, 0.15, size=(4 * n_obs, 3))
+            d = np.maximum(np.maximum((c - h)[:, None] - pts[None], pts[None] - (c + h)[:, None]), 0.0)
+            dist = np.linalg.norm(d, axis=2).min(axis=1)
+            for i in np.nonzero((dist > gap[0]) & (dist < gap[1]))[0][:n_obs - n]:
+                out[s, n] = np.concatenate((c[i] - h[i], c[i] + h[i])); n += 1
+    return out

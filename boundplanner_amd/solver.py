@@ -86,7 +86,7 @@ EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error"
            "bmpc_last_kernel_ms", "bmpc_get_opts", "bmpc_stream", "bmpc_robot_iiwa14", "bmpc_robot_gen3", "bmpc_set_robot", "bmpc_get_robot",
            "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full", "bmpc_debug_lane_stats",
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
-           "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
+           "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_set_scenes", "bmpc_loop_set_rollout_scenes", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
            "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev", "bmpc_default_sets_opts", "bmpc_convex_sets", "bmpc_convex_sets_dev"]
 
@@ -131,6 +131,8 @@ def load_library():
         lib.bmpc_loop_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
         lib.bmpc_loop_destroy.argtypes = [ctypes.c_void_p]
         lib.bmpc_loop_set_obstacles.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _dp, _ip, _dp, _ip]
+        lib.bmpc_loop_set_scenes.argtypes = [ctypes.c_void_p, ctypes.c_int, _ip, _dp, _dp, _ip, _dp, _ip]
+        lib.bmpc_loop_set_rollout_scenes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _ip]
         lib.bmpc_loop_upload.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp, _dp]
         lib.bmpc_loop_download.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp, _dp]
         lib.bmpc_loop_run.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]

@@ -261,7 +261,8 @@ int bmpc_debug_spin(bmpc_handle* h, int ms);
  * name with bmpc_loop_field() (names = LP_FIELDS of boundplanner_amd/csrc/bmpc_loop.hpp).
  * Per-step collision sets (ConvexSetFinder.find_set_collision_avoidance, ConvexSetFinder.py:309-375) are computed on the
  * device too: boxes around the collision points, plus separating halfspaces of the scene obstacles set with
- * bmpc_loop_set_obstacles (shared by all rollouts of the loop).
+ * bmpc_loop_set_obstacles (one scene, every rollout uses it) or with bmpc_loop_set_scenes / bmpc_loop_set_rollout_scenes (a table of
+ * scenes, every rollout names its own).
  * All pointers below are HOST pointers.  The loop borrows the handle's solver and stream: do not use the handle
  * for other solves while a loop call is running.  The loop keeps the handle alive: a bmpc_destroy(handle)
  * issued while loops exist is deferred until the last bmpc_loop_destroy. */
@@ -274,9 +275,27 @@ void bmpc_loop_destroy(bmpc_loop* l);
 const char* bmpc_loop_last_error(const bmpc_loop* l);
 /* scene obstacles (BoundMPC.obstacles as polytopes A x <= b with their vertices; ConvexSetFinder.py:309-375):
  * A [n_obs][15][3] and b [n_obs][15] (first nrows[o] rows used), V [n_obs][32][3] (first nv[o] vertices used);
- * n_obs <= 16; n_obs = 0 clears the scene */
+ * n_obs <= 16; n_obs = 0 clears the scene.  One scene that every rollout of the loop uses; for a scene per rollout see
+ * bmpc_loop_set_scenes below.  Replaces whatever an earlier bmpc_loop_set_obstacles / bmpc_loop_set_scenes installed. */
 int bmpc_loop_set_obstacles(bmpc_loop* l, int n_obs, const double* A, const double* b, const int* nrows, const double* V,
                             const int* nv);
+/* One scene per rollout.  bmpc_loop_set_scenes installs a table of n_scenes scenes: scene s has n_obs[s] obstacles
+ * (0 <= n_obs[s] <= 16); the obstacles of all scenes are stored back to back in scene order, each in the layout of
+ * bmpc_loop_set_obstacles: A [sum n_obs][15][3], b [sum n_obs][15], nrows [sum n_obs], V [sum n_obs][32][3], nv [sum n_obs].
+ * It replaces whatever bmpc_loop_set_obstacles / an earlier bmpc_loop_set_scenes installed (the later call wins, in either order), and
+ * every rollout is assigned scene -1 (no obstacles) afterwards.  n_scenes = 0 clears the table.
+ * bmpc_loop_set_rollout_scenes assigns scene[i] in [-1, n_scenes) to rollouts first .. first+count-1; -1: obstacle-free collision sets.
+ * Both synchronise the loop's stream first, so they may be called between two bmpc_loop_run calls (obstacles that move or appear:
+ * re-install the table, or re-assign rollouts).  Misuse (null pointers, n_obs[s] / row / vertex counts out of range, a scene index or
+ * a rollout range out of range) returns 1 with a message in bmpc_loop_last_error and leaves the loop as it was.
+ * The assignment is configuration of the loop, not state of the rollout: it is not part of the state vector, of
+ * bmpc_loop_download / bmpc_loop_upload or of the records.  A rollout whose scene needs more than 15 rows in a collision set is
+ * frozen (dead = 2) like on the shared scene; the others are not affected.
+ * Device memory: 3108 bytes per obstacle that exists (A, b, A A^T, V, box), about 50 KB for a scene of 16, plus
+ * R * 6 * max n_obs * 64 bytes of closest-pair results. */
+int bmpc_loop_set_scenes(bmpc_loop* l, int n_scenes, const int* n_obs, const double* A, const double* b, const int* nrows,
+                         const double* V, const int* nv);
+int bmpc_loop_set_rollout_scenes(bmpc_loop* l, int first, int count, const int* scene);
 /* state: [count][state_doubles]; prev: [count][n_w] previous solutions (warm start) or NULL */
 int bmpc_loop_upload(bmpc_loop* l, int first, int count, const double* state, const double* prev);
 int bmpc_loop_download(bmpc_loop* l, int first, int count, double* state, double* prev);

@@ -28,8 +28,15 @@ def parser():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--chunk", type=int, default=25, help="MPC steps per bmpc_loop_run call (progress lines)")
     ap.add_argument("--seed", type=int, default=4096)
-    ap.add_argument("--scene", choices=["free", "example"], default="free", help="free: configs[4] (no obstacles); example: the 12 "
-                    "boxes of the reference's example scene, starts scattered around its start configuration, its goal pose")
+    ap.add_argument("--scene", choices=["free", "example", "random"], default="free", help="free: configs[4] (no obstacles); example: the 12 "
+                    "boxes of the reference's example scene, starts scattered around its start configuration, its goal pose; random: the "
+                    "same starts and goal, all rollouts on scene 0 of the --scenes generator (shared: bmpc_loop_set_obstacles)")
+    ap.add_argument("--scenes", type=int, default=0, help="K > 0: one scene per rollout (bmpc_loop_set_scenes) -- K random scenes of "
+                    "--scene-obstacles boxes near the arm's sweep (fixed seed), rollouts assigned round-robin; starts and goal of --scene example")
+    ap.add_argument("--scene-obstacles", type=int, default=12, help="boxes per scene of --scenes / --scene random")
+    ap.add_argument("--loop-per-scene", action="store_true", help="with --scenes K: the alternative a scene table replaces -- K loops (own "
+                    "handle, stream and batched solve) of R / K rollouts with one shared scene each (bmpc_loop_set_obstacles), --groups of "
+                    "them stepped concurrently, the rest in sequence")
     ap.add_argument("--async", dest="async_", action="store_true", help="rollouts do not wait for each other (bmpc_loop_run_async); one group")
     ap.add_argument("--dump-failing", default=None, help="one group only: .npz with the inputs (x0, lbx, ubx, p) of the last step's solves that did not converge, "
                     "and the per-rollout counts of failed solves")
@@ -52,6 +59,11 @@ def run(args, progress=True):
     base = get_default_params()
     params = Params(n=N, dt=base.dt, build=False, weights=base.weights, nr_segs=base.nr_segs)
     G = 1 if args.async_ else max(1, args.groups)
+    conc = G                       # loops stepped concurrently
+    if args.loop_per_scene:
+        if args.scenes < 1 or args.async_:
+            raise SystemExit("--loop-per-scene needs --scenes K and lock step")
+        G = args.scenes
     bounds = [R * g // G for g in range(G + 1)]
     kw = {}
     for kv in args.opt:
@@ -61,13 +73,22 @@ def run(args, progress=True):
     be = bes[0]
     rng = np.random.default_rng(args.seed)
     t0 = time.perf_counter()
-    obs = None
-    if args.scene == "example":
+    obs = table = None
+    t_install, table_bytes = [], 0
+    if args.scene in ("example", "random") or args.scenes > 0:
         boxes, q0, goal_p, goal_r = scenes.example_scene()
-        obs = scenes.boxes_to_sets(boxes)
         q_start = q0 + rng.uniform(-0.15, 0.15, size=(R, 7))
         fs = be.fk(q_start)
         fg = {"ee_pos": np.tile(goal_p, (R, 1)), "ee_rot": np.tile(goal_r, (R, 1, 1))}
+        if args.scene == "random" or args.scenes > 0:
+            clear = np.vstack((fs["col_pts"][::max(1, R // 64)].reshape(-1, 3), fs["ee_pos"][::max(1, R // 64)], goal_p[None]))
+            rboxes = scenes.random_box_scenes(args.seed, max(args.scenes, 1), args.scene_obstacles, clear)
+            if args.scenes > 0:
+                table = [scenes.boxes_to_sets(bx) for bx in rboxes]
+            else:
+                obs = scenes.boxes_to_sets(rboxes[0])
+        else:
+            obs = scenes.boxes_to_sets(boxes)
     else:
         q_start, q_goal = scenes.sample_start_goal(rng, be.fk, R)
         fs, fg = be.fk(q_start), be.fk(q_goal)
@@ -77,6 +98,16 @@ def run(args, progress=True):
     for g, loop in enumerate(loops):
         if obs is not None:
             loop.set_obstacles(*obs)
+        if table is not None and args.loop_per_scene:
+            loop.set_obstacles(*table[g])
+        elif table is not None:             # rollout r of the whole run looks at scene r mod K; a loop gets the scenes its rollouts use
+            of = np.arange(bounds[g], bounds[g + 1]) % len(table)
+            used = np.unique(of)
+            t1 = time.perf_counter()
+            loop.set_scenes([table[i] for i in used], np.searchsorted(used, of))
+            t_install.append(time.perf_counter() - t1)
+            n_o = [len(table[i][0]) for i in used]
+            table_bytes += sum(n_o) * (8 * (45 + 15 + 225 + 96 + 6) + 12) + 4 * (len(used) + 1) + 4 * len(of) + len(of) * 6 * max(n_o) * 64
         for i, r in enumerate(range(bounds[g], bounds[g + 1])):
             loop.set_rollout(i, seed_objs.mpcs[r], seed_objs.q[r], seed_objs.dq[r], seed_objs.ddq[r], seed_objs.jerk[r],
                              seed_objs.qf[r], seed_objs.v[r], seed_objs.p_lie[r])
@@ -111,11 +142,14 @@ def run(args, progress=True):
             parts = [None] * G
             def work(g):
                 parts[g] = loops[g].run(n)
-            th = [threading.Thread(target=work, args=(g,)) for g in range(G)]
-            for t in th: t.start()
-            for t in th: t.join()
+            for w in range(0, G, conc):          # (more loops than --groups: in waves)
+                th = [threading.Thread(target=work, args=(g,)) for g in range(w, min(w + conc, G))]
+                for t in th: t.start()
+                for t in th: t.join()
+                if w > 0:
+                    ms_total += max(l.ms_total for l in loops[w:w + conc]); ms_solve += max(l.ms_solve for l in loops[w:w + conc])
             log = np.concatenate(parts, axis=1)
-        ms_total += max(l.ms_total for l in loops); ms_solve += max(l.ms_solve for l in loops)
+        ms_total += max(l.ms_total for l in loops[:conc]); ms_solve += max(l.ms_solve for l in loops[:conc])
         iters.append(log[:, :, L["iters"]]); fails.append(log[:, :, L["error_count"]] > 0)
         if args.diagnose:
             hist.append(np.concatenate((log[:, :, [L["phi"], L["phi_max"], L["error_count"], L["iters"], L["status"], L["viol"], L["dead"]]],
@@ -147,6 +181,13 @@ def run(args, progress=True):
         "iters_sum_of_per_step_max": int(it.max(axis=1).sum()), "iters_per_rollout_total_max": int(it.sum(axis=0).max()),
         "iters_per_rollout_total_mean": float(it.sum(axis=0).mean()),
     }
+    if table is not None:
+        out.update(scenes=len(table), scene_obstacles=args.scene_obstacles, ms_outside_solve_per_step=(ms_total - ms_solve) / args.steps)
+        if args.loop_per_scene:
+            out.update(loop_per_scene=True, loops_concurrent=conc)
+        else:       # device bytes of all loops' tables (obstacles, offsets, assignment, closest-pair results); install = packing on the
+            #         host + A A^T + upload, per loop (each group's loop holds the scenes its own rollouts use)
+            out.update(scene_table_bytes=table_bytes, scene_table_install_s=sum(t_install), scene_table_install_s_per_loop_max=max(t_install))
     if args.async_:
         out["lanes"] = dict(bes[0].lane_stats(), fast_lane_max=int(os.environ.get("BMPC_FAST_LANE", "0")),
                             reserved_cus=int(os.environ.get("BMPC_FAST_CUS", "0")))
