@@ -646,6 +646,61 @@ extern "C" int bmpc_debug_inst_state(bmpc_handle* h, int B, double* out) {
     return 0;
 }
 
+// test entry (include/boundmpc.h): the stage matrices of B instances at given points, rows and adjoint multipliers.  Host pointers;
+// the call owns the handle's workspace and stream and waits for the result.
+extern "C" int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                         const double* t, const double* z, const double* lam_pi, double* H) {
+    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !lam_pi || !H) { if (h) h->err = "bmpc_debug_stage_matrices: bad argument"; return 1; }
+    int rc = bmpc_wait(h);
+    if (rc) return rc;
+    BUSY_OR_FAIL(h, "bmpc_debug_stage_matrices");
+    WEDGED_FAIL(h);
+    HIPCHK(h, hipSetDevice(h->o.device));
+    if (h->o.hess != 2) { h->err = "bmpc_debug_stage_matrices: needs a handle with the exact Hessian (hess = 2)"; return 1; }
+    if ((rc = pipe_ensure(h, B))) return rc;
+    if (B > h->pipe_cap) { h->err = "bmpc_debug_stage_matrices: more instances than workspace slots"; return 1; }
+    const int N = h->o.N, cap = h->pipe_cap;
+    const size_t n_w = 44 * (size_t)N + 6, S = (size_t)(N - 1);
+    const size_t sz[8] = {B * n_w, B * n_w, B * n_w, (size_t)B * NPAR, B * S * NSLOT, B * S * NSLOT, (size_t)B * N * 3, B * S * NZ * NZ};
+    const double* src[7] = {x0, lbx, ubx, p, t, z, lam_pi};
+    size_t off[9] = {0};
+    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + (sz[i] + 15) / 16 * 16;
+    const size_t n_out = B * n_w + 2 * (size_t)B;                    // x, f, viol of the argument block (never written here)
+    double* d = nullptr;
+    int* di = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d, (off[8] + n_out) * sizeof(double)));
+    if (hipMalloc((void**)&di, 2 * (size_t)B * sizeof(int)) != hipSuccess) { (void)hipFree(d); h->err = "bmpc_debug_stage_matrices: out of device memory"; return 2; }
+    hipStream_t st = h->stream;
+    auto body = [&]() -> int {
+        for (int i = 0; i < 7; i++) HIPCHK(h, hipMemcpyAsync(d + off[i], src[i], sz[i] * sizeof(double), hipMemcpyHostToDevice, st));
+        PipeArgsH A;
+        A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
+        A.o = SolverOpts{N, h->o.dt, h->o.tol, h->o.max_iter, h->o.hess, h->o.hess_switch,
+                         h->o.mu_init, h->o.kappa_mu, h->o.theta_mu, h->o.kappa_eps,
+                         h->o.mu_floor_k, h->o.dw0, h->o.inertia_err, h->o.ls_alpha_mem, h->o.inertia, h->o.stall_n, h->o.gn_backoff, h->o.slack_reset, h->o.trial_repeats};
+        A.rc = h->d_rc;
+        A.x0 = d + off[0]; A.lbx = d + off[1]; A.ubx = d + off[2]; A.p = d + off[3];
+        A.x = d + off[8]; A.f = A.x + B * n_w; A.viol = A.f + B; A.g = nullptr; A.iters = di; A.status = di + B;
+        pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
+        A.st = (InstState*)h->d_pipe_st;
+        A.src = lane_carve(A.L, h->d_pipe_lists, cap);
+        A.tbl = h->d_pipe_tbl;
+        A.prof = h->d_prof;
+        A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
+        h->last_valid = false;
+        int cnt0[NCNT] = {0};
+        cnt0[0] = B; cnt0[6] = B; cnt0[9] = B;
+        HIPCHK(h, hipMemcpyAsync(A.L.cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice, st));
+        HIPCHK(h, bmpc_pipe_launch_init(&A, B, st));
+        HIPCHK(h, bmpc_pipe_launch_stage_matrices(&A, d + off[4], d + off[5], d + off[6], d + off[7], st));
+        HIPCHK(h, hipMemcpyAsync(H, d + off[7], sz[7] * sizeof(double), hipMemcpyDeviceToHost, st));
+        return wait_stream(h, st);
+    };
+    rc = body();
+    if (rc != 5) { (void)hipFree(d); (void)hipFree(di); }      // (a wedged stream may still use them)
+    return rc;
+}
+
 // diagnostic / measurement: HIP events around every launch of the Riccati kernel (bmpc_k_ric: the throughput variant, bmpc_k_ric_lat:
 // the latency variant of nearly empty super-steps) on the handle's stream, from the next solve on.  bmpc_debug_ric_stats returns, for
 // the most recent solve, out[0..2] = {summed launch durations in ms, launches, instance-iterations (workgroups that ran)} of

@@ -36,6 +36,8 @@ hipError_t bmpc_pipe_launch_retire_admit(const bmpc::PipeArgsH* A, int n_max, in
 hipError_t bmpc_pipe_launch_step(bmpc::PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat);
 hipError_t bmpc_pipe_launch_pick(bmpc::PipeArgsH* A0, bmpc::PipeArgsH* A1, const int* prio, int n_max, hipStream_t st);
 hipError_t bmpc_pipe_launch_mult(const bmpc::PipeArgsH* A, hipStream_t st);
+hipError_t bmpc_pipe_launch_stage_matrices(const bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
+                                           double* d_H, hipStream_t st);
 void bmpc_pipe_build_table(int* tbl);
 size_t bmpc_pipe_state_bytes(void);
 

@@ -7,6 +7,7 @@
 #define BMPC_NT 64
 #include "bmpc_pair_kernels.hpp"
 #include "bmpc_ric_kernel.hpp"
+#include "bmpc_stage_matrix.hpp"
 #include "bmpc_internal.hpp"
 
 using namespace bmpc;
@@ -198,10 +199,8 @@ extern "C" hipError_t bmpc_pipe_launch_retire_admit(const PipeArgsH* A, int n_ma
     return hipGetLastError();
 }
 
-// one super-step for at most n_act active instances; swaps the double-buffered lists in *A
-// e0 / e1 (optional): events recorded around the Riccati launch (bmpc_debug_time_ric); *was_lat: which variant was launched
-extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
-    const int nw = waves_for(A->N, n_act);
+// the evaluation launches of a super-step for nw groups of pairs: k_points || k_pose, then k_eval (|| k_curv)
+static void launch_eval(const PipeArgsH* A, int nw, hipStream_t st) {
     static const int split_launches = [] { const char* e = getenv("BMPC_SPLIT_LAUNCHES"); return e ? atoi(e) : 0; }();
     if (split_launches) {
         LAUNCH_DYN(bmpc_k_points, nw, 64, pair_lds_doubles(A->N, false));
@@ -222,6 +221,13 @@ extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t
         else
         hipLaunchKernelGGL(bmpc_k_eval_curv, dim3(A->o.hess == 2 ? 2 * nw : nw), dim3(64), pair_lds_doubles(A->N, true) * sizeof(double), st, *A, nw);
     }
+}
+
+// one super-step for at most n_act active instances; swaps the double-buffered lists in *A
+// e0 / e1 (optional): events recorded around the Riccati launch (bmpc_debug_time_ric); *was_lat: which variant was launched
+extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
+    const int nw = waves_for(A->N, n_act);
+    launch_eval(A, nw, st);
     // BMPC_RIC_LAT_BELOW in the environment (read once): A/B runs and the test that the two variants agree bitwise
     static const int lat_below = [] { const char* e = getenv("BMPC_RIC_LAT_BELOW"); return e ? atoi(e) : BMPC_RIC_LAT_BELOW; }();
     if (e0) (void)hipEventRecord(e0, st);
@@ -272,6 +278,25 @@ extern "C" hipError_t bmpc_pipe_launch_pick(PipeArgsH* A0, PipeArgsH* A1, const 
 extern "C" hipError_t bmpc_pipe_launch_mult(const PipeArgsH* A, hipStream_t st) {
     LAUNCH_DYN(bmpc_k_mult, waves_for(A->N, A->B), 64, pair_lds_doubles(A->N, false));
     LAUNCH(bmpc_k_mult_sweep, (A->B + 63) / 64, 64);
+    return hipGetLastError();
+}
+
+// test entry bmpc_debug_stage_matrices (bmpc_stage_matrix.hpp): kernels of their own beside the product's, which they do not touch
+__global__ __launch_bounds__(64) void bmpc_k_dbg_set_rows(PipeArgsH H, const double* t, const double* z) {
+    k_set_rows_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)t, (GCD)z);
+}
+__global__ __launch_bounds__(BMPC_RIC_NT, 1) void bmpc_k_dbg_stage_matrices(PipeArgsH H, const double* lam_pi, double* Hout) {
+    __shared__ __attribute__((aligned(16))) double lds[RIC_LDS_DOUBLES];
+    k_stage_matrix_body<BMPC_RIC_NT>(ric_kernel_args(), blockIdx.x, threadIdx.x, (LDSD*)lds, (GCD)lam_pi, (GD)Hout);
+}
+// B instances in slots 0 .. B-1, just initialised (bmpc_pipe_launch_init): rows overwritten, the super-step's own evaluation
+// launches once, then the stage matrices
+extern "C" hipError_t bmpc_pipe_launch_stage_matrices(const PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
+                                                      double* d_H, hipStream_t st) {
+    const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
+    hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_t, d_z);
+    launch_eval(A, waves_for(A->N, A->B), st);
+    hipLaunchKernelGGL(bmpc_k_dbg_stage_matrices, dim3(A->B), dim3(BMPC_RIC_NT), 0, st, *A, d_lam_pi, d_H);
     return hipGetLastError();
 }
 

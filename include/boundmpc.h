@@ -233,6 +233,15 @@ int bmpc_debug_phase_cycles(bmpc_handle* h, double* out16);
  * retries, rejected line-search trials, KKT error of the previous iterate, stall counter.  With max_iter = k: the decisions of
  * iteration k - 1, which the iterate-for-iterate parity test compares with the oracle's.  B <= workspace slots. */
 int bmpc_debug_inst_state(bmpc_handle* h, int B, double* out);
+/* Test entry: the stage matrices the Riccati sweep factorises (zeta coordinates, H [B][N-1][41][41], row-major), for B instances
+ * at the points x0 with GIVEN row slacks / multipliers t, z [B][N-1][208] (row slots of csrc/bmpc_device.hpp) and GIVEN adjoint
+ * multipliers of the pi dynamics lam_pi [B][N][3] (stage k uses lam_pi[k+1]).  The slots are initialised by the product's init
+ * launch, t, z and the exact-Hessian switch are overwritten, the product's evaluation launches of a super-step run once, and a
+ * kernel of the entry's own runs the sweep's load phase per stage and copies the matrix out.  Host pointers; B <= workspace
+ * slots; the handle must have been created with hess = 2.  tests/test_hessian_pin_gpu.py compares the result with probes of the
+ * reference's Lagrangian Hessian. */
+int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                              const double* t, const double* z, const double* lam_pi, double* H);
 /* Measurement: from the next solve on, HIP events bracket every launch of the Riccati kernel on the handle's stream
  * (bmpc_debug_time_ric(h, 1)); bmpc_debug_ric_stats then returns for the most recent solve {summed launch durations [ms], launches,
  * instance-iterations} of the throughput variant of that kernel in out6[0..2] and of its latency variant (nearly empty super-steps)

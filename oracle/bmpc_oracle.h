@@ -101,6 +101,15 @@ int bmpc_oracle_solve_batch_info(const bmpc_oracle_opts* o, int B, const double*
                                  const double* lbx, const double* ubx, const double* p, double* x,
                                  double* f, int* iters, int* status, double* viol, double* info, int nthreads);
 
+/* ---- test entries for the second-order pin (tests/test_hessian_pin.py; documented in bmpc_solve.c) ---- */
+#define BMPC_ORACLE_MAXROWS 216
+int bmpc_oracle_stage_rows(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                           int* nrows, int* meta, double* coef);
+int bmpc_oracle_stage_matrices(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                               const double* t, const double* z, const double* lam_pi, double* H);
+int bmpc_oracle_debug_hess(const bmpc_oracle_opts* o, const double* x0, const double* lbx, const double* ubx, const double* p,
+                           int k, double zval, double lamval, double* Hout, double* Hfd);
+
 #ifdef __cplusplus
 }
 #endif

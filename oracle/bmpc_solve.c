@@ -16,8 +16,11 @@
  *   - hat-function dynamics are rewritten x~_{k+1} = A x~_k + b u_k with
  *     x_k = x~_k + B1 u_k, pi_k = p_rot_k - dt/2 w_k, rs~_k = rs_k - dt/2 drs_k (bijective);
  *   - the 6 global dslacks ride along as a constant state;
- *   - the Hessian is Gauss-Newton/convex (exact first derivatives): the KKT points are those
- *     of the reference NLP, the iteration path is not IPOPT's.
+ *   - first derivatives are exact; the Hessian is the Gauss-Newton part far from a solution and the EXACT Hessian of the
+ *     substituted stage Lagrangian (second-order kinematic terms, sigmoid curvature, the pi-dynamics term weighted by the
+ *     adjoint multipliers: assemble_stage with hess = 1, pinned to the reference by tests/test_hessian_pin.py) once the KKT
+ *     error is small, with inertia correction: the KKT points are those of the reference NLP, the iteration path is not
+ *     IPOPT's.
  * The banded KKT system is solved by a dense Riccati recursion (n_x=32, n_u=9).
  * PARITY AT THE IPOPT BOUNDARY IS UNPINNED (see bmpc_oracle.h).
  */
@@ -1559,8 +1562,65 @@ int bmpc_oracle_solve_batch_info(const bmpc_oracle_opts* o, int B, const double*
     return 0;
 }
 
-/* ---- debug: analytic stage Lagrangian Hessian vs central differences of the Lagrangian
- * gradient (tests/test_oracle_solver.py).  Hout/Hfd are NZ x NZ row-major. */
+/* ---- test entries (tests/test_hessian_pin.py) ---- */
+
+/* The rows eval_stage builds at the point w, per stage k = 1 .. N-1, in its own order: nrows[N-1]; meta[N-1][MAXROWS][6] =
+ * {gidx, gsign, xidx, kind, i0, i1}; coef[N-1][MAXROWS][2] = {c0, c1} (KIND_SPARSE rows: h = c0 y[i0] + c1 y[i1] + const).
+ * gidx / gsign are what recover_multipliers uses the other way round: row gidx of the stage's 112 (+ 21 terminal) inequality
+ * rows of g, as g <= ub (+1) or g >= lb (-1). */
+int bmpc_oracle_stage_rows(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                           int* nrows, int* meta, double* coef) {
+    prob_t pb;
+    double pins[40];
+    setup_problem(o, &pb, w, lbx, ubx, p, pins);
+    int N = pb.N;
+    for (int k = N - 1; k >= 1; k--) eval_stage(&pb, k, 0);
+    for (int k = 1; k < N; k++) {
+        const stage_t* s = &pb.st[k];
+        nrows[k - 1] = s->nrows;
+        for (int i = 0; i < s->nrows; i++) {
+            const row_t* r = &s->rows[i];
+            int* m = meta + ((size_t)(k - 1) * MAXROWS + i) * 6;
+            m[0] = r->gidx; m[1] = r->gsign; m[2] = r->xidx; m[3] = r->kind;
+            m[4] = r->kind == KIND_SPARSE ? r->i0 : -1; m[5] = r->kind == KIND_SPARSE ? r->i1 : -1;
+            coef[((size_t)(k - 1) * MAXROWS + i) * 2] = r->c0;
+            coef[((size_t)(k - 1) * MAXROWS + i) * 2 + 1] = r->c1;
+        }
+    }
+    free(pb.st); free(pb.lbq); free(pb.ubq);
+    return MAXROWS;
+}
+
+/* The stage matrices of the Newton system at the point w with GIVEN row slacks / multipliers t, z [N-1][MAXROWS] (row order of
+ * bmpc_oracle_stage_rows) and GIVEN adjoint multipliers of the pi dynamics lam_pi [N][3] (lam_pi[k] multiplies
+ * pi_{k-1} + dt w_{k-1} - pi_k; stage k uses lam_pi[k+1]): eval_stage + assemble_stage with the exact Hessian for every stage,
+ * H [N-1][41][41] in zeta coordinates. */
+int bmpc_oracle_stage_matrices(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                               const double* t, const double* z, const double* lam_pi, double* H) {
+    prob_t pb;
+    double pins[40];
+    setup_problem(o, &pb, w, lbx, ubx, p, pins);
+    int N = pb.N;
+    pb.hess = 1;
+    for (int k = N - 1; k >= 1; k--) eval_stage(&pb, k, 0);
+    for (int k = 1; k < N; k++) {
+        stage_t* s = &pb.st[k];
+        for (int i = 0; i < s->nrows; i++) {
+            s->t[i] = t[(size_t)(k - 1) * MAXROWS + i];
+            s->z[i] = z[(size_t)(k - 1) * MAXROWS + i];
+        }
+        for (int a = 0; a < 3; a++) s->lam[Z_PI + a] = lam_pi[3 * k + a];
+    }
+    for (int k = 1; k < N; k++) {
+        assemble_stage(&pb, k, 0.0);
+        memcpy(H + (size_t)(k - 1) * NZ * NZ, pb.st[k].H, sizeof pb.st[k].H);
+    }
+    free(pb.st); free(pb.lbq); free(pb.ubq);
+    return 0;
+}
+
+/* Analytic stage Lagrangian Hessian (barrier terms left out) against central differences of the stage's own Lagrangian
+ * gradient, entry by entry (tests/test_hessian_pin.py).  Hout/Hfd are NZ x NZ row-major. */
 static void setup_problem(const bmpc_oracle_opts* o, prob_t* pb, const double* x0, const double* lbx,
                           const double* ubx, const double* p, double* pins);
 
@@ -1571,6 +1631,7 @@ int bmpc_oracle_debug_hess(const bmpc_oracle_opts* o, const double* x0, const do
     double pins[40];
     setup_problem(o, &pb, x0, lbx, ubx, p, pins);
     int N = pb.N;
+    pb.hess = 1;
     pb.no_sigma = 1;
     for (int kk = N - 1; kk >= 1; kk--) eval_stage(&pb, kk, 0);
     for (int kk = 1; kk < N; kk++)

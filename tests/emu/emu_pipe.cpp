@@ -24,6 +24,7 @@ static thread_local int t_lane = 0;
 
 #include "../../boundplanner_amd/csrc/bmpc_pair_kernels.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_ric_kernel.hpp"
+#include "../../boundplanner_amd/csrc/bmpc_stage_matrix.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_robot.hpp"
 
 using namespace bmpc;
@@ -127,4 +128,58 @@ extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int he
         launch(nb_inst, [&](int blk, int l) { k_mult_sweep_body(A, blk * 64 + l); });
     }
     return steps;
+}
+
+// The stage matrices the Riccati sweep factorises, at a GIVEN point with GIVEN row slacks / multipliers and adjoint multipliers of
+// the pi dynamics (tests/test_hessian_pin.py): the slots are initialised by the k_init* bodies from x0 = w, then t, z
+// ([B][N-1][NSLOT], slot numbering of bmpc_device.hpp) and hess_mode = 1 are written over the initial ones; k_points, k_pose,
+// k_eval (split = 0: k_eval_body<0>; 1: the two-wavefront pair <2> + <1>) and k_curv run once; then ric_phase_load_impl<128> runs
+// per (instance, stage) with lam_pi[b][k + 1] in R_lam and the stage matrix it leaves in LDS (zeta coordinates) is copied to
+// H [B][N-1][41][41] (k_set_rows_body, k_stage_matrix_body: bmpc_stage_matrix.hpp, the bodies of bmpc_debug_stage_matrices).
+extern "C" int emu_stage_matrices(int N, double dt, int B, const double* w, const double* lbx, const double* ubx, const double* p,
+                                  const double* t, const double* z, const double* lam_pi, int split, double* H) {
+    RobotConst rc;
+    fill_robot_const(rc);
+    PipeArgs A;
+    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
+    A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
+    A.o = SolverOpts{N, dt, 1e-5, 100, 2, 1.0, 0.1, 0.1, 2.0, 1000.0, 1e4, 1e-4, 1e-2, 0.0, 2, 8, 2, 1, 9};
+    A.rc = &rc;
+    A.x0 = w; A.lbx = lbx; A.ubx = ubx; A.p = p;
+    std::vector<double> xo((size_t)B * (44 * N + 6)), fo(B), vo(B);
+    std::vector<int> ito(B), sto(B);
+    A.x = xo.data(); A.f = fo.data(); A.viol = vo.data(); A.g = nullptr; A.iters = ito.data(); A.status = sto.data();
+    const int cap = B;
+    std::vector<double> work(pipe_workspace_doubles(cap, N, 1));
+    pipe_carve(A, work.data(), cap, N, 1);
+    std::vector<InstState> st(cap);
+    std::vector<int> l_eval(cap), l_step(cap), l_trial(cap), l_evn(cap), l_trn(cap), l_done(cap), l_admit(cap), l_curv(cap), srcv(cap), cnt(NCNT, 0), tbl(3 * HREC);
+    build_scatter_table(tbl.data());
+    A.st = st.data();
+    A.L.eval = l_eval.data(); A.L.step = l_step.data(); A.L.trial = l_trial.data();
+    A.L.eval_next = l_evn.data(); A.L.trial_next = l_trn.data(); A.L.cnt = cnt.data();
+    A.L.done = l_done.data(); A.L.admit = l_admit.data(); A.L.curv = l_curv.data(); A.src = srcv.data();
+    A.tbl = tbl.data();
+    std::vector<double> lds(std::max<size_t>(std::max<size_t>(pair_lds_doubles(N, true), trial_lds_doubles(N, 4)), RIC_LDS_DOUBLES) + 64);
+    const int nb_inst = (cap + 63) / 64, nw = waves_for(N, cap);
+    cnt[0] = cap; cnt[6] = cap; cnt[9] = cap;
+    launch(nb_inst, [&](int blk, int l) { k_init_inst_body(A, blk * 64 + l); });
+    launch(nw, [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
+    launch(nb_inst, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
+    k_pool_reset_body(A, false);
+    const size_t nset = (size_t)B * (N - 1) * NSLOT;
+    launch((int)((nset + 63) / 64), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z); });
+    launch(nw, [&](int blk, int l) { k_points_body(A, blk, l, lds.data()); });
+    launch(nw, [&](int blk, int l) { k_pose_body(A, blk, l, lds.data()); });
+    if (split) {
+        launch(nw, [&](int blk, int l) { k_eval_body<2>(A, blk, l, lds.data()); });
+        launch(nw, [&](int blk, int l) { k_eval_body<1>(A, blk, l, lds.data()); });
+    } else
+        launch(nw, [&](int blk, int l) { k_eval_body<0>(A, blk, l, lds.data()); });
+    if (cnt[10] != B) return -1;            // every instance is in the curvature list
+    launch(waves_for(N, cnt[10]), [&](int blk, int l) { k_curv_body(A, blk, l, lds.data()); });
+    launch(B, [&](int b, int lane) {
+        k_stage_matrix_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&A), b, lane, lds.data(), lam_pi, H);
+    }, EMU_RIC_NT);
+    return 0;
 }

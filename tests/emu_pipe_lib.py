@@ -42,3 +42,19 @@ def solve_batch(N, x0, lbx, ubx, p, dt=0.1, tol=1e-5, max_iter=100, hess=2, hess
                                it.ctypes.data_as(_ip), st.ctypes.data_as(_ip), P(viol), verbose, P(lam_g), P(lam_x), slots,
                                D(mu_floor_k), D(dw0), D(inertia_err), inertia, stall_n, gn_backoff, slack_reset, D(ls_alpha_mem), trial_repeats)
     return dict(x=x, g=g, f=f, iters=it, status=st, viol=viol, steps=steps, lam_g=lam_g, lam_x=lam_x)
+
+
+def stage_matrices(N, w, lbx, ubx, p, t, z, lam_pi, dt=0.1, split=0):
+    """emu_stage_matrices: H [B][N-1][41][41] from the kernel bodies at the points w [B][n_w] with row (t, z) [B][N-1][208] in the
+    kernels' slot numbering and lam_pi [B][N][3]; split = 1 runs k_eval as the two-wavefront pair."""
+    lib = ctypes.CDLL(build())
+    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
+    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
+    B = w.shape[0]
+    t, z, lam_pi = (np.ascontiguousarray(a, float) for a in (t, z, lam_pi))
+    assert t.shape == z.shape == (B, N - 1, 208) and lam_pi.shape == (B, N, 3)
+    H = np.zeros((B, N - 1, 41, 41))
+    P = lambda a: a.ctypes.data_as(_dp)
+    rc = lib.emu_stage_matrices(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z), P(lam_pi), split, P(H))
+    assert rc == 0, rc
+    return H

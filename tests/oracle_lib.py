@@ -124,3 +124,51 @@ def solve_batch_info(N, x0, lbx, ubx, p, nthreads=0, **kw):
     lib().bmpc_oracle_solve_batch_info(ctypes.byref(o), B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(x), _P(f),
                                        it.ctypes.data_as(_ip), st.ctypes.data_as(_ip), _P(viol), _P(info), nthreads)
     return dict(x=x, f=f, iters=it, status=st, viol=viol, info=info)
+
+
+MAXROWS = 216
+
+
+def _opts(N, dt):
+    return Opts(N, dt, 1e-5, 100, 0, 1, 1, 1.0, 0.1, 0.1, 2.0, 1000.0, 2, 1e-4, 1e-2, 8, 2, 1, 0.0, 1e4, 0, 0, 0)
+
+
+def _boxes(lbx, ubx):
+    return np.where(np.isinf(lbx), -1e20, lbx), np.where(np.isinf(ubx), 1e20, ubx)
+
+
+def stage_rows(N, w, lbx, ubx, p, dt=0.1):
+    """The rows the oracle builds per stage k = 1 .. N-1 at w (bmpc_oracle_stage_rows): nrows [N-1], meta [N-1][216][6] =
+    (gidx, gsign, xidx, kind, i0, i1), coef [N-1][216][2]."""
+    lbx, ubx = _boxes(lbx, ubx)
+    w, lbx, ubx, p = (np.ascontiguousarray(a, float) for a in (w, lbx, ubx, p))
+    nrows = np.zeros(N - 1, np.int32); meta = np.full((N - 1, MAXROWS, 6), -1, np.int32); coef = np.zeros((N - 1, MAXROWS, 2))
+    o = _opts(N, dt)
+    rc = lib().bmpc_oracle_stage_rows(ctypes.byref(o), _P(w), _P(lbx), _P(ubx), _P(p), nrows.ctypes.data_as(_ip),
+                                      meta.ctypes.data_as(_ip), _P(coef))
+    assert rc == MAXROWS
+    return nrows, meta, coef
+
+
+def stage_matrices(N, w, lbx, ubx, p, t, z, lam_pi, dt=0.1):
+    """Stage matrices H [N-1][41][41] (zeta coordinates, exact Hessian) at w for given row (t, z) [N-1][216] and adjoint
+    multipliers of the pi dynamics lam_pi [N][3] (bmpc_oracle_stage_matrices)."""
+    lbx, ubx = _boxes(lbx, ubx)
+    w, lbx, ubx, p, t, z, lam_pi = (np.ascontiguousarray(a, float) for a in (w, lbx, ubx, p, t, z, lam_pi))
+    assert t.shape == z.shape == (N - 1, MAXROWS) and lam_pi.shape == (N, 3)
+    H = np.zeros((N - 1, 41, 41))
+    o = _opts(N, dt)
+    rc = lib().bmpc_oracle_stage_matrices(ctypes.byref(o), _P(w), _P(lbx), _P(ubx), _P(p), _P(t), _P(z), _P(lam_pi), _P(H))
+    assert rc == 0
+    return H
+
+
+def debug_hess(N, w, lbx, ubx, p, k, zval, lamval, dt=0.1):
+    """(analytic, finite-difference) Lagrangian Hessian of stage k without barrier terms (bmpc_oracle_debug_hess)."""
+    lbx, ubx = _boxes(lbx, ubx)
+    w, lbx, ubx, p = (np.ascontiguousarray(a, float) for a in (w, lbx, ubx, p))
+    Ha, Hf = np.zeros((41, 41)), np.zeros((41, 41))
+    o = _opts(N, dt)
+    lib().bmpc_oracle_debug_hess(ctypes.byref(o), _P(w), _P(lbx), _P(ubx), _P(p), k, ctypes.c_double(zval), ctypes.c_double(lamval),
+                                 _P(Ha), _P(Hf))
+    return Ha, Hf
