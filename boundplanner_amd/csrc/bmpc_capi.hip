@@ -701,6 +701,69 @@ extern "C" int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0
     return rc;
 }
 
+// test entry (include/boundmpc.h): one super-step's Newton step of B instances from given points and rows.  Host pointers; the call
+// owns the handle's workspace and stream and waits for the result.
+extern "C" int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                      const double* t, const double* z, const int* mode, double* dzeta, double* dt, double* dz, double* state) {
+    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !mode || !dzeta || !dt || !dz || !state) {
+        if (h) h->err = "bmpc_debug_newton_step: bad argument";
+        return 1;
+    }
+    for (int i = 0; i < B; i++)
+        if (mode[i] < 0 || mode[i] > 2) { h->err = "bmpc_debug_newton_step: mode must be 0, 1 or 2"; return 1; }
+    int rc = bmpc_wait(h);
+    if (rc) return rc;
+    BUSY_OR_FAIL(h, "bmpc_debug_newton_step");
+    WEDGED_FAIL(h);
+    HIPCHK(h, hipSetDevice(h->o.device));
+    if (h->o.hess != 2) { h->err = "bmpc_debug_newton_step: needs a handle with the exact Hessian (hess = 2)"; return 1; }
+    if ((rc = pipe_ensure(h, B))) return rc;
+    if (B > h->pipe_cap) { h->err = "bmpc_debug_newton_step: more instances than workspace slots"; return 1; }
+    const int N = h->o.N, cap = h->pipe_cap;
+    const size_t n_w = 44 * (size_t)N + 6, S = (size_t)(N - 1);
+    // inputs 0 .. 5, outputs 6 .. 9 (dzeta, dt, dz, state)
+    const size_t sz[10] = {B * n_w, B * n_w, B * n_w, (size_t)B * NPAR, B * S * NSLOT, B * S * NSLOT, B * S * NZ, B * S * NSLOT, B * S * NSLOT, (size_t)B * 12};
+    const double* src[6] = {x0, lbx, ubx, p, t, z};
+    double* dst[4] = {dzeta, dt, dz, state};
+    size_t off[11] = {0};
+    for (int i = 0; i < 10; i++) off[i + 1] = off[i] + (sz[i] + 15) / 16 * 16;
+    const size_t n_out = B * n_w + 2 * (size_t)B;                    // x, f, viol of the argument block (never written here)
+    double* d = nullptr;
+    int* di = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d, (off[10] + n_out) * sizeof(double)));
+    if (hipMalloc((void**)&di, 3 * (size_t)B * sizeof(int)) != hipSuccess) { (void)hipFree(d); h->err = "bmpc_debug_newton_step: out of device memory"; return 2; }
+    hipStream_t st = h->stream;
+    auto body = [&]() -> int {
+        for (int i = 0; i < 6; i++) HIPCHK(h, hipMemcpyAsync(d + off[i], src[i], sz[i] * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(di + 2 * (size_t)B, mode, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+        PipeArgsH A;
+        A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
+        A.o = SolverOpts{N, h->o.dt, h->o.tol, h->o.max_iter, h->o.hess, h->o.hess_switch,
+                         h->o.mu_init, h->o.kappa_mu, h->o.theta_mu, h->o.kappa_eps,
+                         h->o.mu_floor_k, h->o.dw0, h->o.inertia_err, h->o.ls_alpha_mem, h->o.inertia, h->o.stall_n, h->o.gn_backoff, h->o.slack_reset, h->o.trial_repeats};
+        A.rc = h->d_rc;
+        A.x0 = d + off[0]; A.lbx = d + off[1]; A.ubx = d + off[2]; A.p = d + off[3];
+        A.x = d + off[10]; A.f = A.x + B * n_w; A.viol = A.f + B; A.g = nullptr; A.iters = di; A.status = di + B;
+        pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
+        A.st = (InstState*)h->d_pipe_st;
+        A.src = lane_carve(A.L, h->d_pipe_lists, cap);
+        A.tbl = h->d_pipe_tbl;
+        A.prof = h->d_prof;
+        A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
+        h->last_valid = false;
+        int cnt0[NCNT] = {0};
+        cnt0[0] = B; cnt0[6] = B; cnt0[9] = B;
+        HIPCHK(h, hipMemcpyAsync(A.L.cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice, st));
+        HIPCHK(h, bmpc_pipe_launch_init(&A, B, st));
+        HIPCHK(h, bmpc_pipe_launch_newton_step(&A, d + off[4], d + off[5], di + 2 * (size_t)B, d + off[6], d + off[7], d + off[8], d + off[9], st));
+        for (int i = 0; i < 4; i++) HIPCHK(h, hipMemcpyAsync(dst[i], d + off[6 + i], sz[6 + i] * sizeof(double), hipMemcpyDeviceToHost, st));
+        return wait_stream(h, st);
+    };
+    rc = body();
+    if (rc != 5) { (void)hipFree(d); (void)hipFree(di); }      // (a wedged stream may still use them)
+    return rc;
+}
+
 // diagnostic / measurement: HIP events around every launch of the Riccati kernel (bmpc_k_ric: the throughput variant, bmpc_k_ric_lat:
 // the latency variant of nearly empty super-steps) on the handle's stream, from the next solve on.  bmpc_debug_ric_stats returns, for
 // the most recent solve, out[0..2] = {summed launch durations in ms, launches, instance-iterations (workgroups that ran)} of

@@ -38,6 +38,8 @@ hipError_t bmpc_pipe_launch_pick(bmpc::PipeArgsH* A0, bmpc::PipeArgsH* A1, const
 hipError_t bmpc_pipe_launch_mult(const bmpc::PipeArgsH* A, hipStream_t st);
 hipError_t bmpc_pipe_launch_stage_matrices(const bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
                                            double* d_H, hipStream_t st);
+hipError_t bmpc_pipe_launch_newton_step(bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode, double* d_dzeta,
+                                        double* d_dt, double* d_dz, double* d_state, hipStream_t st);
 void bmpc_pipe_build_table(int* tbl);
 size_t bmpc_pipe_state_bytes(void);
 

@@ -223,11 +223,10 @@ static void launch_eval(const PipeArgsH* A, int nw, hipStream_t st) {
     }
 }
 
-// one super-step for at most n_act active instances; swaps the double-buffered lists in *A
+// the factorisation and direction launches of a super-step for at most n_act active instances in nw groups of pairs: the Riccati
+// kernel in the variant the number of live instances selects, k_fwd, k_step
 // e0 / e1 (optional): events recorded around the Riccati launch (bmpc_debug_time_ric); *was_lat: which variant was launched
-extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
-    const int nw = waves_for(A->N, n_act);
-    launch_eval(A, nw, st);
+static void launch_direction(PipeArgsH* A, int n_act, int nw, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
     // BMPC_RIC_LAT_BELOW in the environment (read once): A/B runs and the test that the two variants agree bitwise
     static const int lat_below = [] { const char* e = getenv("BMPC_RIC_LAT_BELOW"); return e ? atoi(e) : BMPC_RIC_LAT_BELOW; }();
     if (e0) (void)hipEventRecord(e0, st);
@@ -248,6 +247,13 @@ extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t
     if (was_lat) *was_lat = n_act < lat_below || n_act < spec_below;      // (the launches of the tail regime, whichever kernels ran)
     LAUNCH(bmpc_k_fwd, n_act, 64);
     LAUNCH_DYN(bmpc_k_step, nw, 64, pair_lds_doubles(A->N, false));
+}
+
+// one super-step for at most n_act active instances; swaps the double-buffered lists in *A
+extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
+    const int nw = waves_for(A->N, n_act);
+    launch_eval(A, nw, st);
+    launch_direction(A, n_act, nw, st, e0, e1, was_lat);
     // (BMPC_TRIAL_REPEATS in the environment, read once, overrides bmpc_opts.trial_repeats: A/B runs)
     static const int env_repeats = [] { const char* e = getenv("BMPC_TRIAL_REPEATS"); return e ? atoi(e) : -1; }();
     if (env_repeats >= 0) A->o.trial_repeats = env_repeats;
@@ -282,8 +288,11 @@ extern "C" hipError_t bmpc_pipe_launch_mult(const PipeArgsH* A, hipStream_t st) 
 }
 
 // test entry bmpc_debug_stage_matrices (bmpc_stage_matrix.hpp): kernels of their own beside the product's, which they do not touch
-__global__ __launch_bounds__(64) void bmpc_k_dbg_set_rows(PipeArgsH H, const double* t, const double* z) {
-    k_set_rows_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)t, (GCD)z);
+__global__ __launch_bounds__(64) void bmpc_k_dbg_set_rows(PipeArgsH H, const double* t, const double* z, const int* mode) {
+    k_set_rows_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)t, (GCD)z, (GCI)mode);
+}
+__global__ __launch_bounds__(64) void bmpc_k_dbg_newton_out(PipeArgsH H, double* dzeta, double* dt, double* dz, double* state) {
+    k_newton_out_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GD)dzeta, (GD)dt, (GD)dz, (GD)state);
 }
 __global__ __launch_bounds__(BMPC_RIC_NT, 1) void bmpc_k_dbg_stage_matrices(PipeArgsH H, const double* lam_pi, double* Hout) {
     __shared__ __attribute__((aligned(16))) double lds[RIC_LDS_DOUBLES];
@@ -294,9 +303,23 @@ __global__ __launch_bounds__(BMPC_RIC_NT, 1) void bmpc_k_dbg_stage_matrices(Pipe
 extern "C" hipError_t bmpc_pipe_launch_stage_matrices(const PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
                                                       double* d_H, hipStream_t st) {
     const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
-    hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_t, d_z);
+    hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_t, d_z, (const int*)nullptr);
     launch_eval(A, waves_for(A->N, A->B), st);
     hipLaunchKernelGGL(bmpc_k_dbg_stage_matrices, dim3(A->B), dim3(BMPC_RIC_NT), 0, st, *A, d_lam_pi, d_H);
+    return hipGetLastError();
+}
+
+// test entry bmpc_debug_newton_step: B instances in slots 0 .. B-1, just initialised; rows and the Hessian mode overwritten, then
+// the evaluation and the factorisation / direction launches of a super-step exactly as bmpc_pipe_launch_step issues them for B
+// live instances -- no trial, no rotate -- and the copy-out
+extern "C" hipError_t bmpc_pipe_launch_newton_step(PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode, double* d_dzeta,
+                                                   double* d_dt, double* d_dz, double* d_state, hipStream_t st) {
+    const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
+    const int nw = waves_for(A->N, A->B);
+    hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_t, d_z, d_mode);
+    launch_eval(A, nw, st);
+    launch_direction(A, A->B, nw, st, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(bmpc_k_dbg_newton_out, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_dzeta, d_dt, d_dz, d_state);
     return hipGetLastError();
 }
 

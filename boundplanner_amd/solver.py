@@ -84,7 +84,7 @@ class BmpcOpts(ctypes.Structure):
 EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error", "bmpc_dims",
            "bmpc_gbounds", "bmpc_solve", "bmpc_solve_dev", "bmpc_solve_dev_async", "bmpc_multipliers_dev", "bmpc_wait", "bmpc_active", "bmpc_fk",
            "bmpc_last_kernel_ms", "bmpc_get_opts", "bmpc_stream", "bmpc_robot_iiwa14", "bmpc_robot_gen3", "bmpc_set_robot", "bmpc_get_robot",
-           "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_stage_matrices", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full", "bmpc_debug_lane_stats",
+           "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_stage_matrices", "bmpc_debug_newton_step", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full", "bmpc_debug_lane_stats",
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_set_scenes", "bmpc_loop_set_rollout_scenes", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
@@ -146,6 +146,7 @@ def load_library():
         lib.bmpc_debug_spin.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.bmpc_debug_inst_state.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp]
         lib.bmpc_debug_stage_matrices.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 8
+        lib.bmpc_debug_newton_step.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 4
         lib.bmpc_debug_time_ric.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.bmpc_debug_ric_stats.argtypes = [ctypes.c_void_p, _dp]
         lib.bmpc_debug_lane_stats.argtypes = [ctypes.c_void_p, _dp]
@@ -260,6 +261,22 @@ class HipBoundMPC:
         self._chk(self.lib.bmpc_debug_stage_matrices(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z), _P(lam_pi), _P(H)),
                   "bmpc_debug_stage_matrices")
         return H
+
+    def newton_step(self, x0, lbx, ubx, p, t, z, mode):
+        """Test entry: the Newton step of one super-step at the points x0 [B][n_w] for given row slacks / multipliers t, z
+        [B][N-1][208] and first-attempt Hessian mode [B] (0 Gauss-Newton, 1 exact, 2 exact + inertia correction on failure):
+        (dzeta [B][N-1][41], dt [B][N-1][208], dz [B][N-1][208], state [B][12]) (bmpc_debug_newton_step)."""
+        lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
+        x0, lbx, ubx, p, t, z = (np.ascontiguousarray(np.atleast_2d(a) if a.ndim < 2 else a, float) for a in (x0, lbx, ubx, p, t, z))
+        B, N = x0.shape[0], self.N
+        mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
+        assert x0.shape == lbx.shape == ubx.shape == (B, 44 * N + 6) and p.shape == (B, 875)
+        assert t.shape == z.shape == (B, N - 1, 208)
+        dzeta, dt, dz, state = np.zeros((B, N - 1, 41)), np.zeros((B, N - 1, 208)), np.zeros((B, N - 1, 208)), np.zeros((B, 12))
+        self._chk(self.lib.bmpc_debug_newton_step(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z),
+                                                  mode.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _P(dzeta), _P(dt), _P(dz), _P(state)),
+                  "bmpc_debug_newton_step")
+        return dzeta, dt, dz, state
 
     def time_ric(self, on=True):
         """HIP events around every launch of the Riccati kernel, from the next solve on (bmpc_debug_time_ric)."""

@@ -242,6 +242,18 @@ int bmpc_debug_inst_state(bmpc_handle* h, int B, double* out);
  * reference's Lagrangian Hessian. */
 int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
                               const double* t, const double* z, const double* lam_pi, double* H);
+/* Test entry: the Newton step of ONE super-step, for B instances at the points x0 with GIVEN row slacks / multipliers
+ * t, z [B][N-1][208] (row slots of csrc/bmpc_device.hpp).  mode [B]: the Hessian of the first factorisation attempt -- 0 Gauss-Newton,
+ * 1 exact, 2 exact with the KKT error of the previous iterate set to 0 (a failed attempt is then answered by delta_w, not by the
+ * Gauss-Newton fallback).  Sequence: the product's init launch, rows and mode overwritten, the product's evaluation launches, the
+ * product's Riccati launch in the variant B live instances select, k_fwd, k_step; no trial point, no list rotation.  Returned per
+ * instance: dzeta [B][N-1][41]; the row steps dt, dz [B][N-1][208] (NaN in the slots k_step did not write: padding slots are left
+ * untouched); state [B][12] with the fields of bmpc_debug_inst_state, where state[1] is -1 when the instance took a step and its
+ * final status (0 converged at entry, 3 every factorisation attempt failed) otherwise, [2] the barrier parameter the forward start
+ * used, [4] / [5] the dual / primal fraction-to-boundary lengths, [6] delta_w, [7] the mode the FIRST attempt ran with, [8] the
+ * retries.  Host pointers; B <= workspace slots; the handle must have been created with hess = 2.  rc 1 on misuse. */
+int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                           const double* t, const double* z, const int* mode, double* dzeta, double* dt, double* dz, double* state);
 /* Measurement: from the next solve on, HIP events bracket every launch of the Riccati kernel on the handle's stream
  * (bmpc_debug_time_ric(h, 1)); bmpc_debug_ric_stats then returns for the most recent solve {summed launch durations [ms], launches,
  * instance-iterations} of the throughput variant of that kernel in out6[0..2] and of its latency variant (nearly empty super-steps)

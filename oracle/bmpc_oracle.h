@@ -107,6 +107,12 @@ int bmpc_oracle_stage_rows(const bmpc_oracle_opts* o, const double* w, const dou
                            int* nrows, int* meta, double* coef);
 int bmpc_oracle_stage_matrices(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
                                const double* t, const double* z, const double* lam_pi, double* H);
+/* the linear system of one interior-point iteration, stage by stage, and optionally the oracle's own step for it
+ * (tests/test_newton_step.py; documented in bmpc_solve.c) */
+int bmpc_oracle_newton_system(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                              const double* t, const double* z, int hess_mode, double mu, double dw, double* H, double* g,
+                              double* gdual, double* A, double* B, double* r, double* r0, double* lam, int* nrows, double* h,
+                              double* a, double* dzeta);
 int bmpc_oracle_debug_hess(const bmpc_oracle_opts* o, const double* x0, const double* lbx, const double* ubx, const double* p,
                            int k, double zval, double lamval, double* Hout, double* Hfd);
 

@@ -1619,6 +1619,94 @@ int bmpc_oracle_stage_matrices(const bmpc_oracle_opts* o, const double* w, const
     return 0;
 }
 
+/* The linear system of ONE interior-point iteration, stated stage by stage (tests/test_newton_step.py solves it densely): at the
+ * point w with GIVEN row slacks / multipliers t, z [N-1][MAXROWS] (row order of bmpc_oracle_stage_rows), the Hessian mode
+ * (0 Gauss-Newton, 1 exact) and a GIVEN barrier parameter mu, in the order of the solve loop -- eval_stage, assemble_stage,
+ * kkt_error (the adjoint multipliers), and with the exact Hessian assemble_stage again with those multipliers:
+ *   H [N-1][41][41] (zeta coordinates, barrier terms in, NO delta_w), g, gdual [N-1][41], A [N-1][32][32], B [N-1][32][9],
+ *   r [N-1][32] (zero at the terminal stage: it has no successor), r0 [24], lam [N][32] (lam[k] = adjoint multipliers of stage k;
+ *   the exact Hessian of stage k is weighted with lam[k+1][pi]), nrows [N-1], h [N-1][MAXROWS], a [N-1][MAXROWS][41] (row
+ *   gradients in zeta coordinates).
+ * dzeta [N-1][41] (may be NULL): the oracle's OWN step for this system with delta_w = dw on the Hessian diagonal in natural
+ * coordinates (assemble_stage with hreg = dw, riccati_backward with the fixed reg = 1e-9 on the control blocks, riccati_forward).
+ * Returns 0, or 1 when dzeta was asked for and a block of the recursion was not positive definite. */
+int bmpc_oracle_newton_system(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                              const double* t, const double* z, int hess_mode, double mu, double dw, double* H, double* g,
+                              double* gdual, double* A, double* B, double* r, double* r0, double* lam, int* nrows, double* h,
+                              double* a, double* dzeta) {
+    prob_t pb;
+    double pins[40];
+    setup_problem(o, &pb, w, lbx, ubx, p, pins);
+    int N = pb.N, rc = 0;
+    pb.hess = hess_mode ? 1 : 0;
+    for (int k = N - 1; k >= 1; k--) eval_stage(&pb, k, 0);
+    for (int k = 1; k < N; k++) {
+        stage_t* s = &pb.st[k];
+        for (int i = 0; i < s->nrows; i++) {
+            s->t[i] = t[(size_t)(k - 1) * MAXROWS + i];
+            s->z[i] = z[(size_t)(k - 1) * MAXROWS + i];
+        }
+    }
+    kkt_t kk;
+    memset(&kk, 0, sizeof kk);
+    for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
+    kkt_error(&pb, &kk, mu);
+    if (pb.hess)
+        for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
+    memset(lam, 0, sizeof(double) * NX);
+    for (int i = 0; i < 24; i++) r0[i] = pb.r0[i];
+    for (int k = 1; k < N; k++) {
+        const stage_t* s = &pb.st[k];
+        const size_t e = (size_t)(k - 1);
+        memcpy(H + e * NZ * NZ, s->H, sizeof s->H);
+        memcpy(g + e * NZ, s->g, sizeof s->g);
+        memcpy(gdual + e * NZ, s->gdual, sizeof s->gdual);
+        memcpy(lam + (size_t)k * NX, s->lam, sizeof s->lam);
+        if (k < N - 1) {
+            memcpy(A + e * NX * NX, s->A, sizeof s->A);
+            memcpy(B + e * NX * NU, s->B, sizeof s->B);
+            memcpy(r + e * NX, s->r, sizeof s->r);
+        } else {
+            memset(A + e * NX * NX, 0, sizeof s->A);
+            memset(B + e * NX * NU, 0, sizeof s->B);
+            memset(r + e * NX, 0, sizeof s->r);
+        }
+        nrows[k - 1] = s->nrows;
+        for (int i = 0; i < s->nrows; i++) {
+            const row_t* rw = &s->rows[i];
+            double ay[NZ];
+            memset(ay, 0, sizeof ay);
+            if (rw->kind == KIND_POSE) {
+                for (int l = 0; l < NLOC; l++)
+                    for (int j = 0; j < NZ; j++) ay[j] += rw->a[l] * s->Jpose[l][j];
+            } else if (rw->kind == KIND_PT) {
+                for (int l = 0; l < 4; l++)
+                    for (int j = 0; j < NZ; j++) ay[j] += rw->a[l] * s->Jpt[rw->grp][l][j];
+            } else {
+                ay[rw->i0] += rw->c0;
+                if (rw->i1 >= 0) ay[rw->i1] += rw->c1;
+            }
+            double* az = a + (e * MAXROWS + i) * NZ;
+            for (int j = 0; j < NZ; j++) {
+                double sm = 0;
+                for (int l = 0; l < NZ; l++) sm += pb.T[l * NZ + j] * ay[l];
+                az[j] = sm;
+            }
+            h[e * MAXROWS + i] = s->h[i];
+        }
+    }
+    if (dzeta) {
+        pb.hreg = dw;
+        if (dw != 0.0)
+            for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
+        if (riccati_backward(&pb, 1e-9) || riccati_forward(&pb)) rc = 1;
+        else
+            for (int k = 1; k < N; k++) memcpy(dzeta + (size_t)(k - 1) * NZ, pb.st[k].dzeta, sizeof pb.st[k].dzeta);
+    }
+    free(pb.st); free(pb.lbq); free(pb.ubq);
+    return rc;
+}
+
 /* Analytic stage Lagrangian Hessian (barrier terms left out) against central differences of the stage's own Lagrangian
  * gradient, entry by entry (tests/test_hessian_pin.py).  Hout/Hfd are NZ x NZ row-major. */
 static void setup_problem(const bmpc_oracle_opts* o, prob_t* pb, const double* x0, const double* lbx,

@@ -183,3 +183,57 @@ extern "C" int emu_stage_matrices(int N, double dt, int B, const double* w, cons
     }, EMU_RIC_NT);
     return 0;
 }
+
+// The Newton step of one super-step from a given state (tests/test_newton_step.py; the bodies of bmpc_debug_newton_step): slots
+// initialised by the k_init* bodies from x0 = w, rows and the first attempt's Hessian mode written over them (k_set_rows_body), then
+// k_points, k_pose, k_eval, k_curv, the Riccati body (variant 0: k_ric_body, the kernels bmpc_k_ric / bmpc_k_ric_lat; 1: the
+// speculative pair k_ric_att_body + k_ric_body<RESUME> with three attempts), k_fwd, k_step, and the copy-out k_newton_out_body.
+extern "C" int emu_newton_step(int N, double dt_, int B, const double* w, const double* lbx, const double* ubx, const double* p,
+                               const double* t, const double* z, const int* mode, int variant, double* dzeta, double* dt, double* dz,
+                               double* state) {
+    RobotConst rc;
+    fill_robot_const(rc);
+    PipeArgs A;
+    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
+    A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
+    A.o = SolverOpts{N, dt_, 1e-5, 100, 2, 1.0, 0.1, 0.1, 2.0, 1000.0, 1e4, 1e-4, 1e-2, 0.0, 2, 8, 2, 1, 9};
+    A.rc = &rc;
+    A.x0 = w; A.lbx = lbx; A.ubx = ubx; A.p = p;
+    std::vector<double> xo((size_t)B * (44 * N + 6)), fo(B), vo(B);
+    std::vector<int> ito(B), sto(B);
+    A.x = xo.data(); A.f = fo.data(); A.viol = vo.data(); A.g = nullptr; A.iters = ito.data(); A.status = sto.data();
+    const int cap = B;
+    std::vector<double> work(pipe_workspace_doubles(cap, N, 1));
+    pipe_carve(A, work.data(), cap, N, 1);
+    std::vector<InstState> st(cap);
+    std::vector<int> l_eval(cap), l_step(cap), l_trial(cap), l_evn(cap), l_trn(cap), l_done(cap), l_admit(cap), l_curv(cap), srcv(cap), cnt(NCNT, 0), tbl(3 * HREC);
+    build_scatter_table(tbl.data());
+    A.st = st.data();
+    A.L.eval = l_eval.data(); A.L.step = l_step.data(); A.L.trial = l_trial.data();
+    A.L.eval_next = l_evn.data(); A.L.trial_next = l_trn.data(); A.L.cnt = cnt.data();
+    A.L.done = l_done.data(); A.L.admit = l_admit.data(); A.L.curv = l_curv.data(); A.src = srcv.data();
+    A.tbl = tbl.data();
+    std::vector<double> lds(std::max<size_t>(std::max<size_t>(pair_lds_doubles(N, true), trial_lds_doubles(N, 4)), RIC_LDS_DOUBLES) + 64);
+    const int nb_inst = (cap + 63) / 64, nw = waves_for(N, cap);
+    cnt[0] = cap; cnt[6] = cap; cnt[9] = cap;
+    launch(nb_inst, [&](int blk, int l) { k_init_inst_body(A, blk * 64 + l); });
+    launch(nw, [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
+    launch(nb_inst, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
+    k_pool_reset_body(A, false);
+    const size_t nset = (size_t)B * (N - 1) * NSLOT;
+    launch((int)((nset + 63) / 64), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z, mode); });
+    launch(nw, [&](int blk, int l) { k_points_body(A, blk, l, lds.data()); });
+    launch(nw, [&](int blk, int l) { k_pose_body(A, blk, l, lds.data()); });
+    launch(nw, [&](int blk, int l) { k_eval_body<0>(A, blk, l, lds.data()); });
+    launch(waves_for(N, cnt[10]), [&](int blk, int l) { k_curv_body(A, blk, l, lds.data()); });
+    if (variant == 1) {
+        A.natt = 3;
+        launch(cnt[0] * A.natt, [&](int blk, int l) { k_ric_att_body<EMU_RIC_NT, false>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
+        launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT, false, true>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
+    } else
+        launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
+    launch(cnt[1], [&](int blk, int l) { k_fwd_body(A, blk, l, lds.data()); });
+    launch(waves_for(N, cnt[1]), [&](int blk, int l) { k_step_body(A, blk, l, lds.data()); });
+    launch((int)((nset + 63) / 64), [&](int blk, int l) { k_newton_out_body(A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
+    return 0;
+}

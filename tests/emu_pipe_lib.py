@@ -58,3 +58,22 @@ def stage_matrices(N, w, lbx, ubx, p, t, z, lam_pi, dt=0.1, split=0):
     rc = lib.emu_stage_matrices(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z), P(lam_pi), split, P(H))
     assert rc == 0, rc
     return H
+
+
+def newton_step(N, w, lbx, ubx, p, t, z, mode, dt=0.1, variant=0):
+    """emu_newton_step: (dzeta [B][N-1][41], dt [B][N-1][208], dz [B][N-1][208], state [B][12]) of one super-step of the kernel
+    bodies at the points w [B][n_w] with row (t, z) [B][N-1][208] and first-attempt Hessian mode [B]; variant = 1 runs the
+    speculative pair of Riccati bodies."""
+    lib = ctypes.CDLL(build())
+    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
+    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
+    B = w.shape[0]
+    t, z = (np.ascontiguousarray(a, float) for a in (t, z))
+    mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
+    assert t.shape == z.shape == (B, N - 1, 208)
+    dzeta, dts, dzs, state = np.zeros((B, N - 1, 41)), np.zeros((B, N - 1, 208)), np.zeros((B, N - 1, 208)), np.zeros((B, 12))
+    P = lambda a: a.ctypes.data_as(_dp)
+    rc = lib.emu_newton_step(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z), mode.ctypes.data_as(_ip), variant,
+                             P(dzeta), P(dts), P(dzs), P(state))
+    assert rc == 0, rc
+    return dzeta, dts, dzs, state

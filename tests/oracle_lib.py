@@ -163,6 +163,30 @@ def stage_matrices(N, w, lbx, ubx, p, t, z, lam_pi, dt=0.1):
     return H
 
 
+def newton_system(N, w, lbx, ubx, p, t, z, hess_mode, mu, dw=0.0, dt=0.1, step=True):
+    """The linear system of one interior-point iteration at w for given row (t, z) [N-1][216], Hessian mode and barrier parameter
+    (bmpc_oracle_newton_system): dict of H [N-1][41][41] (no delta_w), g, gdual [N-1][41], A [N-1][32][32], B [N-1][32][9],
+    r [N-1][32], r0 [24], lam [N][32], nrows [N-1], h [N-1][216], a [N-1][216][41]; with step: dzeta [N-1][41], the oracle's own
+    Riccati step with delta_w = dw (None when its recursion met a block that is not positive definite)."""
+    lbx, ubx = _boxes(lbx, ubx)
+    w, lbx, ubx, p, t, z = (np.ascontiguousarray(a, float) for a in (w, lbx, ubx, p, t, z))
+    assert t.shape == z.shape == (N - 1, MAXROWS)
+    S = N - 1
+    d = dict(H=np.zeros((S, 41, 41)), g=np.zeros((S, 41)), gdual=np.zeros((S, 41)), A=np.zeros((S, 32, 32)), B=np.zeros((S, 32, 9)),
+             r=np.zeros((S, 32)), r0=np.zeros(24), lam=np.zeros((N, 32)), nrows=np.zeros(S, np.int32), h=np.zeros((S, MAXROWS)),
+             a=np.zeros((S, MAXROWS, 41)))
+    dz = np.zeros((S, 41))
+    o = _opts(N, dt)
+    f = lib().bmpc_oracle_newton_system
+    f.restype = ctypes.c_int
+    rc = f(ctypes.byref(o), _P(w), _P(lbx), _P(ubx), _P(p), _P(t), _P(z), int(hess_mode), ctypes.c_double(mu), ctypes.c_double(dw),
+           _P(d["H"]), _P(d["g"]), _P(d["gdual"]), _P(d["A"]), _P(d["B"]), _P(d["r"]), _P(d["r0"]), _P(d["lam"]),
+           d["nrows"].ctypes.data_as(_ip), _P(d["h"]), _P(d["a"]), _P(dz) if step else None)
+    assert rc in (0, 1)
+    d["dzeta"] = dz if (step and rc == 0) else None
+    return d
+
+
 def debug_hess(N, w, lbx, ubx, p, k, zval, lamval, dt=0.1):
     """(analytic, finite-difference) Lagrangian Hessian of stage k without barrier terms (bmpc_oracle_debug_hess)."""
     lbx, ubx = _boxes(lbx, ubx)
