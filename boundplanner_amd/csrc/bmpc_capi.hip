@@ -5,10 +5,12 @@
 #define BMPC_NT 64
 #include "bmpc_handle.hpp"
 #include "bmpc_internal.hpp"
+#include "bmpc_staging.hpp"
 
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 using namespace bmpc;
@@ -106,23 +108,11 @@ extern "C" void bmpc_destroy(bmpc_handle* h) {
     }
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (hipEvent_t e : h->ric_ev) if (e) (void)hipEventDestroy(e);
-    double* bufs[] = {h->d_x0, h->d_lbx, h->d_ubx, h->d_p, h->d_x, h->d_g, h->d_f, h->d_viol};
-    for (double* b : bufs) if (b) (void)hipFree(b);
-    if (h->d_iters) (void)hipFree(h->d_iters);
-    if (h->d_status) (void)hipFree(h->d_status);
-    if (h->d_rc) (void)hipFree(h->d_rc);
-    if (h->d_prof) (void)hipFree(h->d_prof);
-    if (h->d_pipe) (void)hipFree(h->d_pipe);
-    if (h->d_pipe_st) (void)hipFree(h->d_pipe_st);
-    if (h->d_pipe_lists) (void)hipFree(h->d_pipe_lists);
-    if (h->d_pipe_tbl) (void)hipFree(h->d_pipe_tbl);
-    if (h->d_lam_g) (void)hipFree(h->d_lam_g);
-    if (h->d_lam_x) (void)hipFree(h->d_lam_x);
+    void* bufs[] = {h->d_x0, h->d_lbx, h->d_ubx, h->d_p, h->d_x, h->d_g, h->d_f, h->d_viol, h->d_iters, h->d_status, h->d_rc, h->d_prof,
+                    h->d_pipe, h->d_pipe_st, h->d_pipe_lists, h->d_pipe_tbl, h->d_lam_g, h->d_lam_x};
+    for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->h_cnt) (void)hipHostFree(h->h_cnt);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
-    for (hipEvent_t e : {h->ev_fork, h->ev_join_f, h->ev_join_b}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ev0, h->ev1, h->ev_wait, h->ev_fork, h->ev_join_f, h->ev_join_b}) if (e) (void)hipEventDestroy(e);
     for (hipStream_t s : {h->st_fast, h->st_bulk}) if (s) (void)hipStreamDestroy(s);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -267,7 +257,182 @@ static int lanes_ensure(bmpc_handle* h, int reserved_cus, int fast_all) {
     h->lane_cfg[0] = 1; h->lane_cfg[1] = reserved_cus; h->lane_cfg[2] = fast_all;
     return 0;
 }
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static SolverOpts solver_opts(const bmpc_opts& o) {
+    return SolverOpts{o.N, o.dt, o.tol, o.max_iter, o.hess, o.hess_switch, o.mu_init, o.kappa_mu, o.theta_mu, o.kappa_eps,
+                      o.mu_floor_k, o.dw0, o.inertia_err, o.ls_alpha_mem, o.inertia, o.stall_n, o.gn_backoff, o.slack_reset, o.trial_repeats};
+}
+// The argument block of a run over the handle's workspace (pipe_ensure), all of it that does not depend on the caller's arrays: the
+// caller sets x0, lbx, ubx, p, x, f, viol, g, iters, status (and cont).  Whatever the last solve left in the workspace is given up.
+static PipeArgsH pipe_args(bmpc_handle* h, int B) {
+    const int N = h->o.N, cap = h->pipe_cap;
+    PipeArgsH A{};
+    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
+    A.o = solver_opts(h->o);
+    A.rc = h->d_rc;
+    pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
+    A.st = (InstState*)h->d_pipe_st;
+    A.src = lane_carve(A.L, h->d_pipe_lists, cap);
+    A.tbl = h->d_pipe_tbl;
+    A.prof = h->d_prof;
+    A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
+    h->last_valid = false;
+    return A;
+}
+// first fill of the pool: slots 0 .. n0-1 take the first n0 input rows and are initialised.  `ev` (optional) is recorded after the
+// counter upload and before the launches (ev0 of a solve: bmpc_last_kernel_ms starts at the first kernel).
+static int pipe_seed(bmpc_handle* h, const PipeArgsH& A, int n0, hipStream_t st, hipEvent_t ev = nullptr) {
+    for (int& c : h->cnt_seed) c = 0;
+    h->cnt_seed[0] = n0; h->cnt_seed[6] = n0; h->cnt_seed[9] = n0;
+    HIPCHK(h, hipMemcpyAsync(A.L.cnt, h->cnt_seed, sizeof h->cnt_seed, hipMemcpyHostToDevice, st));
+    if (ev) HIPCHK(h, hipEventRecord(ev, st));
+    HIPCHK(h, bmpc_pipe_launch_init(&A, n0, st));
+    return 0;
+}
+
+// one pipe_solve between its set-up, its driver and its epilogue
+struct PipeRun {
+    bmpc_handle* h;
+    int B, cap, n0;                 // rows, slots, slots filled at the start
+    hipStream_t st;
+    PipeArgsH A;                    // the (bulk) lane
+    bmpc_retire_hook hook; void* hook_ctx;
+    int steps = 0, retired = 0;
+};
+// retirement of the (at most n_max) instances of lane AA that finished: outputs, the caller's hook, (re-)admission
+static int retire_lane(PipeRun& R, PipeArgsH& AA, int n_max, int refill, hipStream_t s_) {
+    bmpc_handle* h = R.h;
+    HIPCHK(h, bmpc_pipe_launch_retire_out(&AA, n_max, s_));
+    if (R.hook) { if (int r = R.hook(R.hook_ctx, AA.L.done, AA.L.cnt + 8, n_max, (void*)s_)) { h->err = "retire hook failed"; return r; } }
+    HIPCHK(h, bmpc_pipe_launch_retire_admit(&AA, n_max, refill, s_));
+    return 0;
+}
+// the counters of lane A (and of lane A1, if there is one: zeros otherwise) come back on st; the stream is idle afterwards, so the
+// event pairs of step_timed are collected too
+static int read_counters(bmpc_handle* h, const PipeArgsH& A, const PipeArgsH* A1, hipStream_t st) {
+    HIPCHK(h, hipMemcpyAsync(h->h_cnt, A.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (A1) HIPCHK(h, hipMemcpyAsync(h->h_cnt + NCNT, A1->L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
+    else for (int i = 0; i < NCNT; i++) h->h_cnt[NCNT + i] = 0;
+    if (int r = wait_stream(h, st)) return r;
+    ric_collect(h);
+    return 0;
+}
+
+// Driver of a batch.  The workspace is a pool of `cap` slots.  B <= cap: every instance has its slot (slot = row).  B > cap (a handle
+// created with pool_slots): the rows stream through the pool -- a slot whose instance has finished is retired (outputs written)
+// and takes the next row at the start of the following super-step, so the kernels keep working on ~cap instances until the input
+// runs out and only ONE straggler tail is paid for the whole call.
+// Every instance advances one stage of its own state machine per super-step; finished instances leave the work lists.  The host
+// only needs upper bounds of the list lengths to size the grids, and the retired count to stop: read back every few super-steps.
+static int drive_batch(PipeRun& R) {
+    bmpc_handle* h = R.h;
+    const int B = R.B, cap = R.cap;
+    const hipStream_t st = R.st;
+    const bool streaming = B > cap;
+    int n_act = R.n0, next_row = R.n0;
+    const long max_steps = 12L * (h->o.max_iter + 2) * ((B + cap - 1) / cap + 1);
+    while (R.retired < B && R.steps < max_steps) {
+        const int burst = R.steps < 8 ? 8 : 4;
+        // while input rows are left (as far as the host knows: next_row only grows), finished instances make room before
+        // every super-step; afterwards they are retired once per burst
+        const bool rows_left = streaming && next_row < B;
+        for (int i = 0; i < burst; i++, R.steps++) {
+            if (rows_left && i > 0) { if (int r = retire_lane(R, R.A, cap, 1, st)) return r; }
+            HIPCHK(h, step_timed(h, &R.A, rows_left ? cap : n_act, st));
+        }
+        if (int r = retire_lane(R, R.A, rows_left ? cap : n_act, rows_left ? 1 : 0, st)) return r;
+        if (int r = read_counters(h, R.A, nullptr, st)) return r;
+        R.retired = h->h_cnt[7];
+        next_row = h->h_cnt[6] < B ? h->h_cnt[6] : B;
+        n_act = next_row - R.retired;
+        if (streaming && next_row < B) n_act = cap < B ? cap : B;
+        h->n_active.store(B - R.retired);
+    }
+    return 0;
+}
+
+// Driver of the closed loop without lock step (a retire hook: every row is a rollout, its slot is refilled with the same row's next
+// problem): a burst of super-steps, then the counters come back and exactly the rollouts whose solve finished in this burst (cnt[8],
+// the done list) are retired -- outputs, the caller's hook (post-processing, next problem), re-admission -- with grids sized by that
+// count; nothing is launched when nobody finished.  (Round 3 ran the whole retirement sequence before every super-step with grids
+// sized for all rollouts: ~1 ms of empty launches per super-step.)  A finished rollout waits at most one burst for its next problem.
+// TWO LANES (round 4; d_prio and prio_max > 0).  With one lane every live rollout iterates at the cadence of a full super-step
+// (2.5 ms at 4096 x N=30), and the run lasts as long as the slowest rollout's iterations (13 k of them on configs[4]) times that.
+// Here the rollouts that lag behind (d_prio, at most prio_max: set by the caller's hook from the steps they have left) iterate in a
+// lane of their own -- lists and counters of its own over the SAME slots and state -- on a second stream, several super-steps of a
+// few dozen instances per bulk super-step.  Per-instance arithmetic does not depend on the lane, so the log stays bitwise that of
+// the lock-step loop.
+struct Lanes {
+    bool two;
+    PipeArgsH A1;                   // the fast lane's argument block
+    hipStream_t sb, sf;             // streams of the bulk lane and of the fast lane
+};
+// (enqueued before the pool is seeded)
+static int lanes_start(PipeRun& R, Lanes& L, const int* d_prio, int prio_max) {
+    bmpc_handle* h = R.h;
+    L.two = d_prio && prio_max > 0;
+    L.A1 = R.A;
+    L.sb = L.sf = R.st;
+    if (!L.two) return 0;
+    if (int r = lanes_ensure(h, env_int("BMPC_FAST_CUS", 0), env_int("BMPC_FAST_ALL", 0))) return r;
+    L.sf = h->st_fast; if (h->st_bulk) L.sb = h->st_bulk;
+    lane_carve(L.A1.L, h->d_pipe_lists + lane_list_ints(R.cap), R.cap);
+    HIPCHK(h, hipMemsetAsync(L.A1.L.cnt, 0, NCNT * sizeof(int), R.st));
+    return 0;
+}
+static int drive_closed_loop(PipeRun& R, Lanes& L, const int* d_prio, int prio_max) {
+    bmpc_handle* h = R.h;
+    const int B = R.B;
+    const hipStream_t st = R.st, sb = L.sb, sf = L.sf;
+    const bool two = L.two;
+    PipeArgsH &A = R.A, &A1 = L.A1;
+    const int lane_burst = env_int("BMPC_FAST_BURST", 4);  // super-steps of the bulk lane per burst
+    const int lane_k = env_int("BMPC_FAST_K", 3);          // super-steps of the fast lane per round
+    int n_act = R.n0;
+    while (R.retired < B) {      // (no bound on the super-steps: how long a rollout lasts is the caller's business)
+        const int burst = R.steps < 8 ? 8 : 4;
+        if (two && R.steps >= 8) {
+            // deal the live instances out between the lanes; the bulk lane then runs its burst while the fast lane goes through
+            // rounds of its own -- a few super-steps, counters back, retirement of ITS finished rollouts (hook and re-admission on
+            // the fast lane's stream: they touch those rollouts only) -- until the bulk burst has ended
+            const int n1 = n_act < prio_max ? n_act : prio_max;
+            HIPCHK(h, bmpc_pipe_launch_pick(&A, &A1, d_prio, n_act, st));
+            HIPCHK(h, hipEventRecord(h->ev_fork, st));
+            HIPCHK(h, hipStreamWaitEvent(sf, h->ev_fork, 0));
+            if (sb != st) HIPCHK(h, hipStreamWaitEvent(sb, h->ev_fork, 0));
+            for (int i = 0; i < lane_burst; i++, R.steps++) HIPCHK(h, step_timed(h, &A, n_act, sb));
+            HIPCHK(h, hipEventRecord(h->ev_join_b, sb));
+            h->lane_stats[0] += 1; h->lane_stats[2] += lane_burst;
+            for (int round = 0;; round++) {
+                for (int i = 0; i < lane_k; i++) HIPCHK(h, bmpc_pipe_launch_step(&A1, n1, sf, nullptr, nullptr, nullptr));
+                HIPCHK(h, hipMemcpyAsync(h->h_cnt + NCNT, A1.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, sf));
+                if (int r = wait_stream(h, sf)) return r;
+                const int live1 = h->h_cnt[NCNT + 0] + h->h_cnt[NCNT + 2], nd1 = h->h_cnt[NCNT + 8];
+                h->lane_stats[1] += lane_k; h->lane_stats[3] += live1 + nd1; h->lane_stats[6] += 1;
+                const hipError_t q = hipEventQuery(h->ev_join_b);
+                if (q != hipErrorNotReady) { HIPCHK(h, q); break; }          // the bulk burst is over: join (what the fast lane finished last is retired below)
+                if (live1 + nd1 == 0) break;                                  // nobody in the fast lane
+                if (nd1 > 0) { if (int r = retire_lane(R, A1, nd1, 1, sf)) return r; }
+            }
+            HIPCHK(h, hipEventRecord(h->ev_join_f, sf));
+            HIPCHK(h, hipStreamWaitEvent(st, h->ev_join_f, 0));
+            if (sb != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_join_b, 0));
+        } else {
+            for (int i = 0; i < burst; i++, R.steps++) HIPCHK(h, step_timed(h, &A, n_act, st));
+        }
+        if (int r = read_counters(h, A, two ? &A1 : nullptr, st)) return r;
+        const int n_done = h->h_cnt[8], n_done1 = h->h_cnt[NCNT + 8];
+        if (n_done > 0) { if (int r = retire_lane(R, A, n_done, 1, st)) return r; }
+        if (n_done1 > 0) { if (int r = retire_lane(R, A1, n_done1, 1, st)) return r; }
+        R.retired = h->h_cnt[7] + h->h_cnt[NCNT + 7];      // rows whose rollout has ended (counted by k_admit: one burst behind)
+        if (n_done + n_done1 > 0 && R.retired + n_done + n_done1 >= B) {      // possibly the last ones: their retirement decides whether anybody goes on
+            if (int r = read_counters(h, A, two ? &A1 : nullptr, st)) return r;
+            R.retired = h->h_cnt[7] + h->h_cnt[NCNT + 7];
+        }
+        n_act = B - R.retired;
+        h->n_active.store(B - R.retired);
+    }
+    return 0;
+}
 
 static int pipe_solve(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx,
                       const double* d_p, double* d_x, double* d_g, double* d_f, int* d_iters, int* d_status,
@@ -276,157 +441,34 @@ static int pipe_solve(bmpc_handle* h, int B, const double* d_x0, const double* d
     WEDGED_FAIL(h);
     int rc = pipe_ensure(h, B);
     if (rc) return rc;
-    const int N = h->o.N, cap = h->pipe_cap;
-    PipeArgsH A;
-    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
-    A.o = SolverOpts{N, h->o.dt, h->o.tol, h->o.max_iter, h->o.hess, h->o.hess_switch,
-                     h->o.mu_init, h->o.kappa_mu, h->o.theta_mu, h->o.kappa_eps,
-                     h->o.mu_floor_k, h->o.dw0, h->o.inertia_err, h->o.ls_alpha_mem, h->o.inertia, h->o.stall_n, h->o.gn_backoff, h->o.slack_reset, h->o.trial_repeats};
-    A.rc = h->d_rc;
+    const int cap = h->pipe_cap;
+    PipeRun R{h, B, cap, B < cap ? B : cap, st, pipe_args(h, B), hook, hook_ctx};
+    PipeArgsH& A = R.A;
     A.x0 = d_x0; A.lbx = d_lbx; A.ubx = d_ubx; A.p = d_p;
     A.x = d_x; A.f = d_f; A.viol = d_viol; A.g = d_g; A.iters = d_iters; A.status = d_status;
-    pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
-    A.st = (InstState*)h->d_pipe_st;
-    A.src = lane_carve(A.L, h->d_pipe_lists, cap);
-    A.tbl = h->d_pipe_tbl;
-    A.prof = h->d_prof;
-    A.lam_g = nullptr; A.lam_x = nullptr;
     A.cont = d_cont;
-    h->last_valid = false;
-    if (hook && B > cap) { h->err = "closed-loop solve: more rollouts than workspace slots"; return 1; }
-    auto retire_lane = [&](PipeArgsH& AA, int n_max, int refill, hipStream_t s_) -> int {
-        HIPCHK(h, bmpc_pipe_launch_retire_out(&AA, n_max, s_));
-        if (hook) { if (int r = hook(hook_ctx, AA.L.done, AA.L.cnt + 8, n_max, (void*)s_)) { h->err = "retire hook failed"; return r; } }
-        HIPCHK(h, bmpc_pipe_launch_retire_admit(&AA, n_max, refill, s_));
-        return 0;
-    };
-    auto retire = [&](int n_max, int refill) -> int { return retire_lane(A, n_max, refill, st); };
-    // Closed loop without lock step, TWO LANES (round 4).  With one lane every live rollout iterates at the cadence of a full
-    // super-step (2.5 ms at 4096 x N=30), and the run lasts as long as the slowest rollout's iterations (13 k of them on
-    // configs[4]) times that.  Here the rollouts that lag behind (d_prio, at most prio_max: set by the caller's hook from the
-    // steps they have left) iterate in a lane of their own -- lists and counters of its own over the SAME slots and state --
-    // on a second stream, several super-steps of a few dozen instances per bulk super-step.  Per-instance arithmetic does not
-    // depend on the lane, so the log stays bitwise that of the lock-step loop.
-    const bool two = hook && d_prio && prio_max > 0;
-    PipeArgsH A1 = A;
-    hipStream_t sb = st, sf = st;
-    const int lane_burst = env_int("BMPC_FAST_BURST", 4);  // super-steps of the bulk lane per burst
-    const int lane_k = env_int("BMPC_FAST_K", 3);          // super-steps of the fast lane per round
-    if (two) {
-        if (int r = lanes_ensure(h, env_int("BMPC_FAST_CUS", 0), env_int("BMPC_FAST_ALL", 0))) return r;
-        sf = h->st_fast; if (h->st_bulk) sb = h->st_bulk;
-        lane_carve(A1.L, h->d_pipe_lists + lane_list_ints(cap), cap);
-        HIPCHK(h, hipMemsetAsync(A1.L.cnt, 0, NCNT * sizeof(int), st));
+    Lanes L;
+    if (hook) {
+        if (B > cap) { h->err = "closed-loop solve: more rollouts than workspace slots"; return 1; }
+        if (int r = lanes_start(R, L, d_prio, prio_max)) return r;
+        for (double& v : h->lane_stats) v = 0;
     }
-    if (hook) for (double& v : h->lane_stats) v = 0;
-    // The workspace is a pool of `cap` slots.  B <= cap: every instance has its slot (slot = row).  B > cap (a handle
-    // created with pool_slots): the rows stream through the pool -- a slot whose instance has finished is retired
-    // (outputs written) and takes the next row at the start of the following super-step, so the kernels keep working on
-    // ~cap instances until the input runs out and only ONE straggler tail is paid for the whole call.
-    const int n0 = B < cap ? B : cap;
-    const bool streaming = B > cap || hook != nullptr;      // slots are refilled (closed loop: with the same row's next problem)
-    int cnt0[NCNT] = {0};
-    cnt0[0] = n0; cnt0[6] = n0; cnt0[9] = n0;
-    HIPCHK(h, hipMemcpyAsync(A.L.cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipEventRecord(h->ev0, st));
-    HIPCHK(h, bmpc_pipe_launch_init(&A, n0, st));
-    // Every instance advances one stage of its own state machine per super-step; finished instances leave the work
-    // lists.  The host only needs upper bounds of the list lengths to size the grids, and the retired count to stop:
-    // read back every few super-steps.
-    int n_act = n0, steps = 0, retired = 0, next_row = n0;
+    if (int r = pipe_seed(h, A, R.n0, st, h->ev0)) return r;
     h->n_active.store(B);
     h->ric_pending = 0; h->ric_ms[0] = h->ric_ms[1] = 0; h->ric_launches[0] = h->ric_launches[1] = 0;
-    h->ric_full_n = n0; h->ric_full[0] = h->ric_full[1] = h->ric_full[2] = 0;
-    const long max_steps = hook ? (1L << 40) : 12L * (h->o.max_iter + 2) * ((B + cap - 1) / cap + 1);
-    while (retired < B && steps < max_steps) {
-        const int burst = steps < 8 ? 8 : 4;
-        if (hook) {
-            // closed loop without lock step: a burst of super-steps, then the counters come back and exactly the rollouts whose
-            // solve finished in this burst (cnt[8], the done list) are retired -- outputs, the caller's hook (post-processing, next
-            // problem), re-admission -- with grids sized by that count; nothing is launched when nobody finished.  (Round 3 ran
-            // the whole retirement sequence before every super-step with grids sized for all rollouts: ~1 ms of empty launches
-            // per super-step.)  A finished rollout waits at most one burst for its next problem.
-            if (two && steps >= 8) {
-                // deal the live instances out between the lanes; the bulk lane then runs its burst while the fast lane goes through
-                // rounds of its own -- a few super-steps, counters back, retirement of ITS finished rollouts (hook and re-admission on
-                // the fast lane's stream: they touch those rollouts only) -- until the bulk burst has ended
-                const int n1 = n_act < prio_max ? n_act : prio_max;
-                HIPCHK(h, bmpc_pipe_launch_pick(&A, &A1, d_prio, n_act, st));
-                HIPCHK(h, hipEventRecord(h->ev_fork, st));
-                HIPCHK(h, hipStreamWaitEvent(sf, h->ev_fork, 0));
-                if (sb != st) HIPCHK(h, hipStreamWaitEvent(sb, h->ev_fork, 0));
-                for (int i = 0; i < lane_burst; i++, steps++) HIPCHK(h, step_timed(h, &A, n_act, sb));
-                HIPCHK(h, hipEventRecord(h->ev_join_b, sb));
-                h->lane_stats[0] += 1; h->lane_stats[2] += lane_burst;
-                for (int round = 0;; round++) {
-                    for (int i = 0; i < lane_k; i++) HIPCHK(h, bmpc_pipe_launch_step(&A1, n1, sf, nullptr, nullptr, nullptr));
-                    HIPCHK(h, hipMemcpyAsync(h->h_cnt + NCNT, A1.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, sf));
-                    if (int r = wait_stream(h, sf)) return r;
-                    const int live1 = h->h_cnt[NCNT + 0] + h->h_cnt[NCNT + 2], nd1 = h->h_cnt[NCNT + 8];
-                    h->lane_stats[1] += lane_k; h->lane_stats[3] += live1 + nd1; h->lane_stats[6] += 1;
-                    const hipError_t q = hipEventQuery(h->ev_join_b);
-                    if (q != hipErrorNotReady) { HIPCHK(h, q); break; }          // the bulk burst is over: join (what the fast lane finished last is retired below)
-                    if (live1 + nd1 == 0) break;                                  // nobody in the fast lane
-                    if (nd1 > 0) { if (int r = retire_lane(A1, nd1, 1, sf)) return r; }
-                }
-                HIPCHK(h, hipEventRecord(h->ev_join_f, sf));
-                HIPCHK(h, hipStreamWaitEvent(st, h->ev_join_f, 0));
-                if (sb != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_join_b, 0));
-            } else {
-                for (int i = 0; i < burst; i++, steps++) HIPCHK(h, step_timed(h, &A, n_act, st));
-            }
-            auto read_counters = [&]() -> int {
-                HIPCHK(h, hipMemcpyAsync(h->h_cnt, A.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
-                if (two) HIPCHK(h, hipMemcpyAsync(h->h_cnt + NCNT, A1.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
-                else for (int i = 0; i < NCNT; i++) h->h_cnt[NCNT + i] = 0;
-                return wait_stream(h, st);
-            };
-            if (int r = read_counters()) return r;
-            ric_collect(h);
-            const int n_done = h->h_cnt[8], n_done1 = h->h_cnt[NCNT + 8];
-            if (n_done > 0) { if (int r = retire(n_done, 1)) return r; }
-            if (n_done1 > 0) { if (int r = retire_lane(A1, n_done1, 1, st)) return r; }
-            retired = h->h_cnt[7] + h->h_cnt[NCNT + 7];      // rows whose rollout has ended (counted by k_admit: one burst behind)
-            if (n_done + n_done1 > 0 && retired + n_done + n_done1 >= B) {      // possibly the last ones: their retirement decides whether anybody goes on
-                if (int r = read_counters()) return r;
-                retired = h->h_cnt[7] + h->h_cnt[NCNT + 7];
-            }
-            n_act = B - retired;
-            h->n_active.store(B - retired);
-            continue;
-        }
-        // while input rows are left (as far as the host knows: next_row only grows), finished instances make room before
-        // every super-step; afterwards they are retired once per burst
-        const bool rows_left = streaming && next_row < B;
-        for (int i = 0; i < burst; i++, steps++) {
-            if (rows_left && i > 0) { if (int r = retire(cap, 1)) return r; }
-            HIPCHK(h, step_timed(h, &A, rows_left ? cap : n_act, st));
-        }
-        if (int r = retire(rows_left ? cap : n_act, rows_left ? 1 : 0)) return r;
-        HIPCHK(h, hipMemcpyAsync(h->h_cnt, A.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (int r = wait_stream(h, st)) return r;
-        ric_collect(h);
-        retired = h->h_cnt[7];
-        next_row = h->h_cnt[6] < B ? h->h_cnt[6] : B;
-        n_act = next_row - retired;
-        if (streaming && next_row < B) n_act = cap < B ? cap : B;
-        h->n_active.store(B - retired);
-    }
-    h->last_steps = steps;
+    h->ric_full_n = R.n0; h->ric_full[0] = h->ric_full[1] = h->ric_full[2] = 0;
+    if (int r = hook ? drive_closed_loop(R, L, d_prio, prio_max) : drive_batch(R)) return r;
+    const bool two = hook && L.two;
+    h->last_steps = R.steps;
     h->ric_sweeps[0] = h->h_cnt[11] + (two ? h->h_cnt[NCNT + 11] : 0); h->ric_sweeps[1] = h->h_cnt[12] + (two ? h->h_cnt[NCNT + 12] : 0);
     HIPCHK(h, hipEventRecord(h->ev1, st));
-    // the outputs are complete and the per-handle workspace is free when the call returns (the loop above synchronised)
+    // the outputs are complete and the per-handle workspace is free when the call returns (the drivers synchronised)
     if (int r = wait_stream(h, st)) return r;
-    if (retired < B) { h->err = "pipeline did not drain (internal error)"; return 3; }
+    if (R.retired < B) { h->err = "pipeline did not drain (internal error)"; return 3; }
+    const bool streaming = B > cap || hook != nullptr;      // slots were refilled (closed loop: with the same row's next problem)
     h->last_args = A; h->last_valid = !streaming;      // multipliers need every instance's final iterate in its slot
     h->last_args.cont = nullptr;
     return 0;
-}
-
-static int launch(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx,
-                  const double* d_p, double* d_x, double* d_g, double* d_f, int* d_iters, int* d_status,
-                  double* d_viol, hipStream_t st) {
-    return pipe_solve(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, d_g, d_f, d_iters, d_status, d_viol, st);
 }
 
 extern "C" int bmpc_solve_dev(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx,
@@ -441,7 +483,7 @@ extern "C" int bmpc_solve_dev(bmpc_handle* h, int B, const double* d_x0, const d
     if (B == 0) return 0;
     BUSY_OR_FAIL(h, "bmpc_solve_dev");
     HIPCHK(h, hipSetDevice(h->o.device));
-    return launch(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, d_g, d_f, d_iters, d_status, d_viol, (hipStream_t)stream);
+    return pipe_solve(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, d_g, d_f, d_iters, d_status, d_viol, (hipStream_t)stream);
 }
 
 // (bmpc_internal.hpp; called by bmpc_loop.hip)
@@ -494,7 +536,7 @@ extern "C" int bmpc_solve_dev_async(bmpc_handle* h, int B, const double* d_x0, c
     h->worker = std::thread([=]() {      // the worker owns the handle until it is done (bmpc_wait joins it)
         int r = 0;
         if (hipSetDevice(h->o.device) != hipSuccess) { h->err = "hipSetDevice failed in the worker"; r = 2; }
-        if (r == 0) r = launch(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, d_g, d_f, d_iters, d_status, d_viol, h->stream);
+        if (r == 0) r = pipe_solve(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, d_g, d_f, d_iters, d_status, d_viol, h->stream);
         if (r == 0) r = wait_stream(h, h->stream);
         h->worker_rc = r;
         if (r != 0) h->n_active.store(0);        // a failed solve is not "active" for ever; bmpc_wait reports the code
@@ -520,25 +562,25 @@ extern "C" int bmpc_multipliers_dev(bmpc_handle* h, int B, double* d_lam_g, doub
     return 0;
 }
 
+// a typed device buffer of the handle: freed if set, null, then `count` elements allocated (0: none)
+template <class T> static int dev_realloc(bmpc_handle* h, T** p, size_t count) {
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (count) HIPCHK(h, hipMalloc((void**)p, count * sizeof(T)));
+    return 0;
+}
+
 static int ensure_cap(bmpc_handle* h, int B, bool want_g) {
     if (B <= h->cap && (!want_g || h->cap_g)) return 0;
     int cap = B > h->cap ? B : h->cap;
     if (h->o.max_batch > cap) cap = h->o.max_batch;
-    double** bufs[] = {&h->d_x0, &h->d_lbx, &h->d_ubx, &h->d_x};
-    for (double** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; HIPCHK(h, hipMalloc((void**)b, (size_t)cap * h->n_w * sizeof(double))); }
-    if (h->d_p) (void)hipFree(h->d_p);
-    HIPCHK(h, hipMalloc((void**)&h->d_p, (size_t)cap * NPAR * sizeof(double)));
-    if (h->d_f) (void)hipFree(h->d_f);
-    HIPCHK(h, hipMalloc((void**)&h->d_f, (size_t)cap * sizeof(double)));
-    if (h->d_viol) (void)hipFree(h->d_viol);
-    HIPCHK(h, hipMalloc((void**)&h->d_viol, (size_t)cap * sizeof(double)));
-    if (h->d_iters) (void)hipFree(h->d_iters);
-    HIPCHK(h, hipMalloc((void**)&h->d_iters, (size_t)cap * sizeof(int)));
-    if (h->d_status) (void)hipFree(h->d_status);
-    HIPCHK(h, hipMalloc((void**)&h->d_status, (size_t)cap * sizeof(int)));
-    if (h->d_g) { (void)hipFree(h->d_g); h->d_g = nullptr; }
+    const size_t c = (size_t)cap;
+    for (double** b : {&h->d_x0, &h->d_lbx, &h->d_ubx, &h->d_x}) if (int r = dev_realloc(h, b, c * h->n_w)) return r;
+    if (int r = dev_realloc(h, &h->d_p, c * NPAR)) return r;
+    for (double** b : {&h->d_f, &h->d_viol}) if (int r = dev_realloc(h, b, c)) return r;
+    for (int** b : {&h->d_iters, &h->d_status}) if (int r = dev_realloc(h, b, c)) return r;
     h->cap_g = false;
-    if (want_g) { HIPCHK(h, hipMalloc((void**)&h->d_g, (size_t)cap * h->n_g * sizeof(double))); h->cap_g = true; }
+    if (int r = dev_realloc(h, &h->d_g, want_g ? c * h->n_g : 0)) return r;
+    h->cap_g = want_g;
     h->cap = cap;
     return 0;
 }
@@ -570,8 +612,8 @@ extern "C" int bmpc_solve(bmpc_handle* h, int B, const double* x0, const double*
     HIPCHK(h, hipMemcpyAsync(h->d_lbx, lbx, nw, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->d_ubx, ubx, nw, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->d_p, p, (size_t)B * NPAR * sizeof(double), hipMemcpyHostToDevice, st));
-    rc = launch(h, B, h->d_x0, h->d_lbx, h->d_ubx, h->d_p, h->d_x, g ? h->d_g : nullptr, h->d_f, h->d_iters,
-                h->d_status, h->d_viol, st);
+    rc = pipe_solve(h, B, h->d_x0, h->d_lbx, h->d_ubx, h->d_p, h->d_x, g ? h->d_g : nullptr, h->d_f, h->d_iters,
+                    h->d_status, h->d_viol, st);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(x, h->d_x, nw, hipMemcpyDeviceToHost, st));
     if (g) HIPCHK(h, hipMemcpyAsync(g, h->d_g, (size_t)B * h->n_g * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -583,11 +625,9 @@ extern "C" int bmpc_solve(bmpc_handle* h, int B, const double* x0, const double*
     HIPCHK(h, hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
     if (lam_g || lam_x) {
         if (B > h->cap_lam) {
-            if (h->d_lam_g) { (void)hipFree(h->d_lam_g); h->d_lam_g = nullptr; }
-            if (h->d_lam_x) { (void)hipFree(h->d_lam_x); h->d_lam_x = nullptr; }
             h->cap_lam = 0;
-            HIPCHK(h, hipMalloc((void**)&h->d_lam_g, (size_t)B * h->n_g * sizeof(double)));
-            HIPCHK(h, hipMalloc((void**)&h->d_lam_x, (size_t)B * h->n_w * sizeof(double)));
+            if (int r = dev_realloc(h, &h->d_lam_g, (size_t)B * h->n_g)) return r;
+            if (int r = dev_realloc(h, &h->d_lam_x, (size_t)B * h->n_w)) return r;
             h->cap_lam = B;
         }
         rc = bmpc_multipliers_dev(h, B, h->d_lam_g, h->d_lam_x, st);
@@ -646,122 +686,74 @@ extern "C" int bmpc_debug_inst_state(bmpc_handle* h, int B, double* out) {
     return 0;
 }
 
-// test entry (include/boundmpc.h): the stage matrices of B instances at given points, rows and adjoint multipliers.  Host pointers;
-// the call owns the handle's workspace and stream and waits for the result.
-extern "C" int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                         const double* t, const double* z, const double* lam_pi, double* H) {
-    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !lam_pi || !H) { if (h) h->err = "bmpc_debug_stage_matrices: bad argument"; return 1; }
+// The two test entries (include/boundmpc.h).  Host pointers; the call owns the handle's workspace and stream and waits for the result.
+// What both do before they touch their arrays -- `refusal`: what the entry found wrong with its arguments (null: nothing); `busy`
+// holds the handle for the entry from here on.
+static int debug_prologue(bmpc_handle* h, int B, const char* name, const char* refusal, std::optional<BusyGuard>& busy) {
+    const std::string what = std::string(name) + ": ";
+    if (refusal) { if (h) h->err = what + refusal; return 1; }
     int rc = bmpc_wait(h);
     if (rc) return rc;
-    BUSY_OR_FAIL(h, "bmpc_debug_stage_matrices");
+    busy.emplace(h);
+    if (!busy->ok) return 4;
     WEDGED_FAIL(h);
     HIPCHK(h, hipSetDevice(h->o.device));
-    if (h->o.hess != 2) { h->err = "bmpc_debug_stage_matrices: needs a handle with the exact Hessian (hess = 2)"; return 1; }
+    if (h->o.hess != 2) { h->err = what + "needs a handle with the exact Hessian (hess = 2)"; return 1; }
     if ((rc = pipe_ensure(h, B))) return rc;
-    if (B > h->pipe_cap) { h->err = "bmpc_debug_stage_matrices: more instances than workspace slots"; return 1; }
-    const int N = h->o.N, cap = h->pipe_cap;
-    const size_t n_w = 44 * (size_t)N + 6, S = (size_t)(N - 1);
-    const size_t sz[8] = {B * n_w, B * n_w, B * n_w, (size_t)B * NPAR, B * S * NSLOT, B * S * NSLOT, (size_t)B * N * 3, B * S * NZ * NZ};
-    const double* src[7] = {x0, lbx, ubx, p, t, z, lam_pi};
-    size_t off[9] = {0};
-    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + (sz[i] + 15) / 16 * 16;
-    const size_t n_out = B * n_w + 2 * (size_t)B;                    // x, f, viol of the argument block (never written here)
-    double* d = nullptr;
-    int* di = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, (off[8] + n_out) * sizeof(double)));
-    if (hipMalloc((void**)&di, 2 * (size_t)B * sizeof(int)) != hipSuccess) { (void)hipFree(d); h->err = "bmpc_debug_stage_matrices: out of device memory"; return 2; }
-    hipStream_t st = h->stream;
-    auto body = [&]() -> int {
-        for (int i = 0; i < 7; i++) HIPCHK(h, hipMemcpyAsync(d + off[i], src[i], sz[i] * sizeof(double), hipMemcpyHostToDevice, st));
-        PipeArgsH A;
-        A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
-        A.o = SolverOpts{N, h->o.dt, h->o.tol, h->o.max_iter, h->o.hess, h->o.hess_switch,
-                         h->o.mu_init, h->o.kappa_mu, h->o.theta_mu, h->o.kappa_eps,
-                         h->o.mu_floor_k, h->o.dw0, h->o.inertia_err, h->o.ls_alpha_mem, h->o.inertia, h->o.stall_n, h->o.gn_backoff, h->o.slack_reset, h->o.trial_repeats};
-        A.rc = h->d_rc;
-        A.x0 = d + off[0]; A.lbx = d + off[1]; A.ubx = d + off[2]; A.p = d + off[3];
-        A.x = d + off[8]; A.f = A.x + B * n_w; A.viol = A.f + B; A.g = nullptr; A.iters = di; A.status = di + B;
-        pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
-        A.st = (InstState*)h->d_pipe_st;
-        A.src = lane_carve(A.L, h->d_pipe_lists, cap);
-        A.tbl = h->d_pipe_tbl;
-        A.prof = h->d_prof;
-        A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
-        h->last_valid = false;
-        int cnt0[NCNT] = {0};
-        cnt0[0] = B; cnt0[6] = B; cnt0[9] = B;
-        HIPCHK(h, hipMemcpyAsync(A.L.cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice, st));
-        HIPCHK(h, bmpc_pipe_launch_init(&A, B, st));
-        HIPCHK(h, bmpc_pipe_launch_stage_matrices(&A, d + off[4], d + off[5], d + off[6], d + off[7], st));
-        HIPCHK(h, hipMemcpyAsync(H, d + off[7], sz[7] * sizeof(double), hipMemcpyDeviceToHost, st));
-        return wait_stream(h, st);
-    };
-    rc = body();
-    if (rc != 5) { (void)hipFree(d); (void)hipFree(di); }      // (a wedged stream may still use them)
-    return rc;
+    if (B > h->pipe_cap) { h->err = what + "more instances than workspace slots"; return 1; }
+    return 0;
 }
 
-// test entry (include/boundmpc.h): one super-step's Newton step of B instances from given points and rows.  Host pointers; the call
-// owns the handle's workspace and stream and waits for the result.
+// the stage matrices of B instances at given points, rows and adjoint multipliers
+extern "C" int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                         const double* t, const double* z, const double* lam_pi, double* H) {
+    const bool bad = !h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !lam_pi || !H;
+    std::optional<BusyGuard> busy;
+    if (int rc = debug_prologue(h, B, "bmpc_debug_stage_matrices", bad ? "bad argument" : nullptr, busy)) return rc;
+    const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT;
+    double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
+    int *iters = nullptr, *status = nullptr;
+    Staging s;
+    s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
+    s.in(&t, rows); s.in(&z, rows); s.in(&lam_pi, B * N * 3);
+    s.out(&H, B * (N - 1) * NZ * NZ);
+    s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
+    const hipStream_t st = h->stream;
+    return s.run(h, st, [&]() -> int {
+        PipeArgsH A = pipe_args(h, B);
+        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
+        A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
+        if (int r = pipe_seed(h, A, B, st)) return r;
+        HIPCHK(h, bmpc_pipe_launch_stage_matrices(&A, t, z, lam_pi, H, st));
+        return 0;
+    });
+}
+
+// one super-step's Newton step of B instances from given points and rows
 extern "C" int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
                                       const double* t, const double* z, const int* mode, double* dzeta, double* dt, double* dz, double* state) {
-    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !mode || !dzeta || !dt || !dz || !state) {
-        if (h) h->err = "bmpc_debug_newton_step: bad argument";
-        return 1;
-    }
-    for (int i = 0; i < B; i++)
-        if (mode[i] < 0 || mode[i] > 2) { h->err = "bmpc_debug_newton_step: mode must be 0, 1 or 2"; return 1; }
-    int rc = bmpc_wait(h);
-    if (rc) return rc;
-    BUSY_OR_FAIL(h, "bmpc_debug_newton_step");
-    WEDGED_FAIL(h);
-    HIPCHK(h, hipSetDevice(h->o.device));
-    if (h->o.hess != 2) { h->err = "bmpc_debug_newton_step: needs a handle with the exact Hessian (hess = 2)"; return 1; }
-    if ((rc = pipe_ensure(h, B))) return rc;
-    if (B > h->pipe_cap) { h->err = "bmpc_debug_newton_step: more instances than workspace slots"; return 1; }
-    const int N = h->o.N, cap = h->pipe_cap;
-    const size_t n_w = 44 * (size_t)N + 6, S = (size_t)(N - 1);
-    // inputs 0 .. 5, outputs 6 .. 9 (dzeta, dt, dz, state)
-    const size_t sz[10] = {B * n_w, B * n_w, B * n_w, (size_t)B * NPAR, B * S * NSLOT, B * S * NSLOT, B * S * NZ, B * S * NSLOT, B * S * NSLOT, (size_t)B * 12};
-    const double* src[6] = {x0, lbx, ubx, p, t, z};
-    double* dst[4] = {dzeta, dt, dz, state};
-    size_t off[11] = {0};
-    for (int i = 0; i < 10; i++) off[i + 1] = off[i] + (sz[i] + 15) / 16 * 16;
-    const size_t n_out = B * n_w + 2 * (size_t)B;                    // x, f, viol of the argument block (never written here)
-    double* d = nullptr;
-    int* di = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, (off[10] + n_out) * sizeof(double)));
-    if (hipMalloc((void**)&di, 3 * (size_t)B * sizeof(int)) != hipSuccess) { (void)hipFree(d); h->err = "bmpc_debug_newton_step: out of device memory"; return 2; }
-    hipStream_t st = h->stream;
-    auto body = [&]() -> int {
-        for (int i = 0; i < 6; i++) HIPCHK(h, hipMemcpyAsync(d + off[i], src[i], sz[i] * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(di + 2 * (size_t)B, mode, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-        PipeArgsH A;
-        A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
-        A.o = SolverOpts{N, h->o.dt, h->o.tol, h->o.max_iter, h->o.hess, h->o.hess_switch,
-                         h->o.mu_init, h->o.kappa_mu, h->o.theta_mu, h->o.kappa_eps,
-                         h->o.mu_floor_k, h->o.dw0, h->o.inertia_err, h->o.ls_alpha_mem, h->o.inertia, h->o.stall_n, h->o.gn_backoff, h->o.slack_reset, h->o.trial_repeats};
-        A.rc = h->d_rc;
-        A.x0 = d + off[0]; A.lbx = d + off[1]; A.ubx = d + off[2]; A.p = d + off[3];
-        A.x = d + off[10]; A.f = A.x + B * n_w; A.viol = A.f + B; A.g = nullptr; A.iters = di; A.status = di + B;
-        pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
-        A.st = (InstState*)h->d_pipe_st;
-        A.src = lane_carve(A.L, h->d_pipe_lists, cap);
-        A.tbl = h->d_pipe_tbl;
-        A.prof = h->d_prof;
-        A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
-        h->last_valid = false;
-        int cnt0[NCNT] = {0};
-        cnt0[0] = B; cnt0[6] = B; cnt0[9] = B;
-        HIPCHK(h, hipMemcpyAsync(A.L.cnt, cnt0, sizeof cnt0, hipMemcpyHostToDevice, st));
-        HIPCHK(h, bmpc_pipe_launch_init(&A, B, st));
-        HIPCHK(h, bmpc_pipe_launch_newton_step(&A, d + off[4], d + off[5], di + 2 * (size_t)B, d + off[6], d + off[7], d + off[8], d + off[9], st));
-        for (int i = 0; i < 4; i++) HIPCHK(h, hipMemcpyAsync(dst[i], d + off[6 + i], sz[6 + i] * sizeof(double), hipMemcpyDeviceToHost, st));
-        return wait_stream(h, st);
-    };
-    rc = body();
-    if (rc != 5) { (void)hipFree(d); (void)hipFree(di); }      // (a wedged stream may still use them)
-    return rc;
+    const char* refusal = nullptr;
+    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !mode || !dzeta || !dt || !dz || !state) refusal = "bad argument";
+    else for (int i = 0; i < B; i++) if (mode[i] < 0 || mode[i] > 2) refusal = "mode must be 0, 1 or 2";
+    std::optional<BusyGuard> busy;
+    if (int rc = debug_prologue(h, B, "bmpc_debug_newton_step", refusal, busy)) return rc;
+    const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT;
+    double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
+    int *iters = nullptr, *status = nullptr;
+    Staging s;
+    s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
+    s.in(&t, rows); s.in(&z, rows); s.in(&mode, (size_t)B);
+    s.out(&dzeta, B * (N - 1) * NZ); s.out(&dt, rows); s.out(&dz, rows); s.out(&state, (size_t)B * 12);
+    s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
+    const hipStream_t st = h->stream;
+    return s.run(h, st, [&]() -> int {
+        PipeArgsH A = pipe_args(h, B);
+        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
+        A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
+        if (int r = pipe_seed(h, A, B, st)) return r;
+        HIPCHK(h, bmpc_pipe_launch_newton_step(&A, t, z, mode, dzeta, dt, dz, state, st));
+        return 0;
+    });
 }
 
 // diagnostic / measurement: HIP events around every launch of the Riccati kernel (bmpc_k_ric: the throughput variant, bmpc_k_ric_lat:

@@ -2,6 +2,7 @@
 // stream (wait_stream), the refusal of a handle that ran into its watchdog (WEDGED_FAIL) and of a second concurrent call
 // (BusyGuard).  Shared by the files that implement the C ABI (bmpc_capi.hip, bmpc_capi_batch.hip); BMPC_NT is defined by them.
 #pragma once
+#include "bmpc_internal.hpp"
 #include "bmpc_pipeline.hpp"
 #include "bmpc_robot.hpp"
 
@@ -21,13 +22,14 @@ struct bmpc_handle {
     // workspace (grown on demand to the largest batch seen)
     int pipe_cap = 0;
     // workspace layout (pipe_carve): slot-major; BMPC_LAYOUT=0 in the environment selects the field-major layout of round 1 (A/B runs)
-    int slot_major = [] { const char* e = getenv("BMPC_LAYOUT"); return e ? atoi(e) : 1; }();
+    int slot_major = env_int("BMPC_LAYOUT", 1);
     double* d_pipe = nullptr;      // one slab: SoA iterate/row arrays, stage records, gains, partials
     void* d_pipe_st = nullptr;     // InstState[cap]
     int* d_pipe_lists = nullptr;   // 8 lists + the slot -> row map of cap ints each + NCNT counters; then the same block again for
                                    // the fast lane of the closed loop without lock step (pipe_solve)
     int* d_pipe_tbl = nullptr;     // scatter table of the stage record
     int* h_cnt = nullptr;          // pinned host copy of the counters (2 x NCNT: bulk lane, fast lane)
+    int cnt_seed[bmpc::NCNT] = {0};   // source of the counter upload that seeds the pool (pipe_seed): outlives the enqueued copy
     // closed loop without lock step, two lanes: streams of the fast lane / of the bulk lane (null: the caller's stream), fork / join events
     hipStream_t st_fast = nullptr, st_bulk = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join_f = nullptr, ev_join_b = nullptr;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdlib>
 
 struct bmpc_handle;
 namespace bmpc {
@@ -15,6 +16,10 @@ struct SetScene;
 template <int DEV> struct PipeArgsT;
 typedef PipeArgsT<0> PipeArgsH;
 }  // namespace bmpc
+
+// an integer knob of the environment (A/B runs, tests), `dflt` when it is not set: the one place that reads one.  When a knob is
+// read -- once per process, per handle, per call -- is its caller's business.
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 extern "C" {
 // bmpc_fk.hip

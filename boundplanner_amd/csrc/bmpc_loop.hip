@@ -555,7 +555,7 @@ extern "C" int bmpc_loop_run_async(bmpc_loop* L, int nsteps, double* log, float*
     // fast lane for the rollouts that lag behind: at most BMPC_FAST_LANE of them.  Off unless asked for: measured on configs[4]
     // (EXPERIMENTS.md) it does not pay yet -- a super-step of a few dozen instances beside the bulk lane takes 0.85 - 1.1 ms
     // (0.64 ms on an empty GPU), no faster than the bulk lane's own once half of the rollouts have finished
-    { const char* e = getenv("BMPC_FAST_LANE"); L->prio_max = e ? atoi(e) : 0; }
+    L->prio_max = env_int("BMPC_FAST_LANE", 0);
     LCHK(L, hipMemsetAsync(L->d_prio, 0, (size_t)L->R * sizeof(int), L->st));
     std::vector<int> left((size_t)L->R, nsteps);
     LCHK(L, hipMemcpyAsync(L->d_steps_left, left.data(), left.size() * sizeof(int), hipMemcpyHostToDevice, L->st));

@@ -3,6 +3,7 @@
 // bmpc_capi.hip (pipe_solve).
 #include "bmpc_platform_hip.hpp"
 #include <cstdlib>
+#include <utility>
 
 #define BMPC_NT 64
 #include "bmpc_pair_kernels.hpp"
@@ -201,25 +202,23 @@ extern "C" hipError_t bmpc_pipe_launch_retire_admit(const PipeArgsH* A, int n_ma
 
 // the evaluation launches of a super-step for nw groups of pairs: k_points || k_pose, then k_eval (|| k_curv)
 static void launch_eval(const PipeArgsH* A, int nw, hipStream_t st) {
-    static const int split_launches = [] { const char* e = getenv("BMPC_SPLIT_LAUNCHES"); return e ? atoi(e) : 0; }();
+    static const int split_launches = env_int("BMPC_SPLIT_LAUNCHES", 0);
+    static const int eval_split_wgs = env_int("BMPC_EVAL_SPLIT_WGS", BMPC_EVAL_SPLIT_WGS);      // (read once; 0 = never)
     if (split_launches) {
         LAUNCH_DYN(bmpc_k_points, nw, 64, pair_lds_doubles(A->N, false));
         LAUNCH_DYN(bmpc_k_pose, nw, 64, pair_lds_doubles(A->N, false));
-        static const int eval_split_wgs_s = [] { const char* e = getenv("BMPC_EVAL_SPLIT_WGS"); return e ? atoi(e) : BMPC_EVAL_SPLIT_WGS; }();
-        if (nw <= eval_split_wgs_s) {
+        if (nw <= eval_split_wgs) {
             LAUNCH_DYN(bmpc_k_eval_main, nw, 64, pair_lds_doubles(A->N, true));
             LAUNCH_DYN(bmpc_k_eval_chain, nw, 64, pair_lds_doubles(A->N, true));
         } else
-        LAUNCH_DYN(bmpc_k_eval, nw, 64, pair_lds_doubles(A->N, true));
+            LAUNCH_DYN(bmpc_k_eval, nw, 64, pair_lds_doubles(A->N, true));
         LAUNCH(bmpc_k_curv, nw, 64);
     } else if (nw > 0) {
         hipLaunchKernelGGL(bmpc_k_points_pose, dim3(2 * nw), dim3(64), pair_lds_doubles(A->N, false) * sizeof(double), st, *A, nw);
-        // BMPC_EVAL_SPLIT_WGS (read once; 0 = never)
-        static const int eval_split_wgs = [] { const char* e = getenv("BMPC_EVAL_SPLIT_WGS"); return e ? atoi(e) : BMPC_EVAL_SPLIT_WGS; }();
         if (nw <= eval_split_wgs)
             hipLaunchKernelGGL(bmpc_k_eval_curv_split, dim3(A->o.hess == 2 ? 3 * nw : 2 * nw), dim3(64), pair_lds_doubles(A->N, true) * sizeof(double), st, *A, nw);
         else
-        hipLaunchKernelGGL(bmpc_k_eval_curv, dim3(A->o.hess == 2 ? 2 * nw : nw), dim3(64), pair_lds_doubles(A->N, true) * sizeof(double), st, *A, nw);
+            hipLaunchKernelGGL(bmpc_k_eval_curv, dim3(A->o.hess == 2 ? 2 * nw : nw), dim3(64), pair_lds_doubles(A->N, true) * sizeof(double), st, *A, nw);
     }
 }
 
@@ -228,14 +227,14 @@ static void launch_eval(const PipeArgsH* A, int nw, hipStream_t st) {
 // e0 / e1 (optional): events recorded around the Riccati launch (bmpc_debug_time_ric); *was_lat: which variant was launched
 static void launch_direction(PipeArgsH* A, int n_act, int nw, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
     // BMPC_RIC_LAT_BELOW in the environment (read once): A/B runs and the test that the two variants agree bitwise
-    static const int lat_below = [] { const char* e = getenv("BMPC_RIC_LAT_BELOW"); return e ? atoi(e) : BMPC_RIC_LAT_BELOW; }();
+    static const int lat_below = env_int("BMPC_RIC_LAT_BELOW", BMPC_RIC_LAT_BELOW);
     if (e0) (void)hipEventRecord(e0, st);
     // BMPC_RIC_SPEC_BELOW (read once; 0 = never): below it the factorisation attempts of an iteration run side by side
-    static const int spec_below = [] { const char* e = getenv("BMPC_RIC_SPEC_BELOW"); return e ? atoi(e) : BMPC_RIC_SPEC_BELOW; }();
+    static const int spec_below = env_int("BMPC_RIC_SPEC_BELOW", BMPC_RIC_SPEC_BELOW);
     if (n_act < spec_below && n_act > 0) {
         // as many attempts per instance as the chip holds at once: up to 512 workgroups with the latency compilation of the sweeps
         // (two per CU), up to 1536 with the throughput compilation (six per CU)
-        static const int natt_env = [] { const char* e = getenv("BMPC_RIC_NATT"); return e ? atoi(e) : 0; }();
+        static const int natt_env = env_int("BMPC_RIC_NATT", 0);
         int natt = natt_env > 0 ? natt_env : (n_act * RIC_NATT <= 512 ? RIC_NATT : 1536 / n_act);
         A->natt = natt < 2 ? 2 : (natt > RIC_NATT ? RIC_NATT : natt);
         if (n_act * A->natt <= 512) LAUNCH(bmpc_k_ric_att, n_act * A->natt, BMPC_RIC_NT);
@@ -249,22 +248,23 @@ static void launch_direction(PipeArgsH* A, int n_act, int nw, hipStream_t st, hi
     LAUNCH_DYN(bmpc_k_step, nw, 64, pair_lds_doubles(A->N, false));
 }
 
+// the host's view of the double-buffered lists after bmpc_k_rotate: the *_next lists are the current ones
+static void swap_lists(PipeArgsH* A) { std::swap(A->L.eval, A->L.eval_next); std::swap(A->L.trial, A->L.trial_next); }
 // one super-step for at most n_act active instances; swaps the double-buffered lists in *A
 extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat) {
     const int nw = waves_for(A->N, n_act);
     launch_eval(A, nw, st);
     launch_direction(A, n_act, nw, st, e0, e1, was_lat);
     // (BMPC_TRIAL_REPEATS in the environment, read once, overrides bmpc_opts.trial_repeats: A/B runs)
-    static const int env_repeats = [] { const char* e = getenv("BMPC_TRIAL_REPEATS"); return e ? atoi(e) : -1; }();
+    static const int env_repeats = env_int("BMPC_TRIAL_REPEATS", -1);
     if (env_repeats >= 0) A->o.trial_repeats = env_repeats;
     // BMPC_TRIAL_SPEC_WGS (read once; 0 = never): up to that many groups of pairs the step lengths of a line search are tried side by side (slot-major layout)
-    static const int trial_spec_wgs = [] { const char* e = getenv("BMPC_TRIAL_SPEC_WGS"); return e ? atoi(e) : BMPC_TRIAL_SPEC_WGS; }();
+    static const int trial_spec_wgs = env_int("BMPC_TRIAL_SPEC_WGS", BMPC_TRIAL_SPEC_WGS);
     if (nw <= trial_spec_wgs && A->NP == (size_t)(A->N - 1)) LAUNCH_DYN(bmpc_k_trial_spec, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
     else
-    LAUNCH_DYN(bmpc_k_trial, nw, 64 * BMPC_TRIAL_NW, trial_lds_doubles(A->N, BMPC_TRIAL_NW));      // trial points (+ multiplier update) + filter test, backtracking inside
+        LAUNCH_DYN(bmpc_k_trial, nw, 64 * BMPC_TRIAL_NW, trial_lds_doubles(A->N, BMPC_TRIAL_NW));      // trial points (+ multiplier update) + filter test, backtracking inside
     LAUNCH(bmpc_k_rotate, 1, 64);
-    int* t = A->L.eval; A->L.eval = A->L.eval_next; A->L.eval_next = t;
-    t = A->L.trial; A->L.trial = A->L.trial_next; A->L.trial_next = t;
+    swap_lists(A);
     return hipGetLastError();
 }
 
@@ -274,8 +274,7 @@ extern "C" hipError_t bmpc_pipe_launch_pick(PipeArgsH* A0, PipeArgsH* A1, const 
     hipLaunchKernelGGL(bmpc_k_pick, dim3((n_max + 63) / 64), dim3(64), 0, st, *A0, *A1, prio);
     for (PipeArgsH* A : {A0, A1}) {
         hipLaunchKernelGGL(bmpc_k_rotate, dim3(1), dim3(64), 0, st, *A);
-        int* t = A->L.eval; A->L.eval = A->L.eval_next; A->L.eval_next = t;
-        t = A->L.trial; A->L.trial = A->L.trial_next; A->L.trial_next = t;
+        swap_lists(A);
     }
     return hipGetLastError();
 }

@@ -50,46 +50,110 @@ template <class F> static void launch(int nblocks, F body, int nt = 64) {
     for (auto& t : th) t.join();
 }
 
+static bool env_on(const char* name) { const char* e = getenv(name); return e && atoi(e); }      // read at call time: the tests set the knobs with monkeypatch
+// bmpc_default_opts, for the two test entries
+static SolverOpts default_opts(int N, double dt) { return SolverOpts{N, dt, 1e-5, 100, 2, 1.0, 0.1, 0.1, 2.0, 1000.0, 1e4, 1e-4, 1e-2, 0.0, 2, 8, 2, 1, 9}; }
+
+// Everything a run of the kernel bodies needs beside the caller's arrays -- workspace, instance state, lists, counters, scatter table,
+// LDS buffer -- with a PipeArgs wired to it, and the launch sequences of bmpc_pipeline.hip (bmpc_pipe_launch_init, launch_eval,
+// launch_direction) as members.  A points into the rig: it is neither copied nor moved.
+struct Rig {
+    const int N, cap;           // pool of `cap` slots
+    const int nb_inst, nw;      // grids over all slots: threads per instance / groups of pairs
+    RobotConst rc;
+    PipeArgs A;                 // emulation: BMPC_AS1 is empty, host and device views coincide
+    std::vector<double> work, lds, xo, fo, vo;
+    std::vector<InstState> st;
+    std::vector<int> list[9], cnt, tbl, ito, sto;
+
+    Rig(int B, int cap_, int slot_major, const SolverOpts& o, const double* x0, const double* lbx, const double* ubx, const double* p)
+        : N(o.N), cap(cap_), nb_inst((cap_ + 63) / 64), nw(waves_for(o.N, cap_)), work(pipe_workspace_doubles(cap_, o.N, slot_major)),
+          lds(std::max<size_t>(std::max<size_t>(pair_lds_doubles(o.N, true), trial_lds_doubles(o.N, 4)), RIC_LDS_DOUBLES) + 64),
+          st(cap_), cnt(NCNT, 0), tbl(3 * HREC) {
+        fill_robot_const(rc);
+        A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
+        A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
+        A.o = o;
+        A.rc = &rc;
+        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
+        pipe_carve(A, work.data(), cap, N, slot_major);
+        for (auto& v : list) v.resize(cap);
+        build_scatter_table(tbl.data());
+        A.st = st.data();
+        A.L.eval = list[0].data(); A.L.step = list[1].data(); A.L.trial = list[2].data();
+        A.L.eval_next = list[3].data(); A.L.trial_next = list[4].data(); A.L.cnt = cnt.data();
+        A.L.done = list[5].data(); A.L.admit = list[6].data(); A.L.curv = list[7].data(); A.src = list[8].data();
+        A.tbl = tbl.data();
+    }
+    Rig(const Rig&) = delete;
+    Rig& operator=(const Rig&) = delete;
+
+    // the argument block's outputs of a test entry that has none of its own: x, f, viol, iters, status of B rows (never read)
+    void own_outputs() {
+        xo.resize((size_t)A.B * (44 * N + 6)); fo.resize(A.B); vo.resize(A.B); ito.resize(A.B); sto.resize(A.B);
+        A.x = xo.data(); A.f = fo.data(); A.viol = vo.data(); A.g = nullptr; A.iters = ito.data(); A.status = sto.data();
+    }
+    // bmpc_pipe_launch_init: every slot takes an input row
+    void init() {
+        cnt[0] = cap; cnt[6] = cap; cnt[9] = cap;
+        launch(nb_inst, [&](int blk, int l) { k_init_inst_body(A, blk * 64 + l); });
+        launch(nw, [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
+        launch(nb_inst, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
+        k_pool_reset_body(A, false);
+    }
+    // (the test entries) rows, and with `mode` the first attempt's Hessian mode, written over the initial ones
+    size_t nset() const { return (size_t)A.B * (N - 1) * NSLOT; }
+    void set_rows(const double* t, const double* z, const int* mode = nullptr) {
+        launch((int)((nset() + 63) / 64), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z, mode); });
+    }
+    // launch_eval for n groups of pairs: k_points, k_pose, k_eval (split: the two-wavefront pair of the tail regime on the GPU), then
+    // k_curv for the curvature list -- which must have n_curv entries if that is given (false, k_curv not run, otherwise)
+    bool eval(int n, bool split, int n_curv = -1) {
+        launch(n, [&](int blk, int l) { k_points_body(A, blk, l, lds.data()); });
+        launch(n, [&](int blk, int l) { k_pose_body(A, blk, l, lds.data()); });
+        if (split) {
+            launch(n, [&](int blk, int l) { k_eval_body<2>(A, blk, l, lds.data()); });
+            launch(n, [&](int blk, int l) { k_eval_body<1>(A, blk, l, lds.data()); });
+        } else
+            launch(n, [&](int blk, int l) { k_eval_body<0>(A, blk, l, lds.data()); });
+        if (n_curv >= 0 && cnt[10] != n_curv) return false;
+        launch(waves_for(N, cnt[10]), [&](int blk, int l) { k_curv_body(A, blk, l, lds.data()); });
+        return true;
+    }
+    // launch_direction: the Riccati body (spec: the speculative pair with three attempts, the deep tail's kernels on the GPU), k_fwd, k_step
+    void direction(bool spec) {
+        const PipeArgsH& AH = *reinterpret_cast<const PipeArgsH*>(&A);
+        if (spec) {
+            A.natt = 3;
+            launch(cnt[0] * A.natt, [&](int blk, int l) { k_ric_att_body<EMU_RIC_NT, false>(AH, blk, l, lds.data()); }, EMU_RIC_NT);
+            launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT, false, true>(AH, blk, l, lds.data()); }, EMU_RIC_NT);
+        } else
+            launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT>(AH, blk, l, lds.data()); }, EMU_RIC_NT);
+        launch(cnt[1], [&](int blk, int l) { k_fwd_body(A, blk, l, lds.data()); });
+        launch(waves_for(N, cnt[1]), [&](int blk, int l) { k_step_body(A, blk, l, lds.data()); });
+    }
+};
+
 extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int hess, double hess_switch, double mu_init,
                               double kappa_mu, double theta_mu, double kappa_eps, int B, const double* x0,
                               const double* lbx, const double* ubx, const double* p, double* x, double* g, double* f,
                               int* iters, int* status, double* viol, int verbose, double* lam_g, double* lam_x, int slots,
                               double mu_floor_k, double dw0, double inertia_err, int inertia, int stall_n, int gn_backoff, int slack_reset, double ls_alpha_mem, int trial_repeats) {
-    RobotConst rc;
-    fill_robot_const(rc);
-    PipeArgs A;   // emulation: BMPC_AS1 is empty, host and device views coincide
-    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
-    A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
-    A.o = SolverOpts{N, dt, tol, max_iter, hess, hess_switch, mu_init, kappa_mu, theta_mu, kappa_eps, mu_floor_k, dw0, inertia_err, ls_alpha_mem, inertia, stall_n, gn_backoff, slack_reset, trial_repeats};
-    A.rc = &rc;
-    A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
-    A.x = x; A.f = f; A.viol = viol; A.g = g; A.iters = iters; A.status = status;
     const int cap = (slots > 0 && slots < B) ? slots : B;       // pool of `cap` slots: B > cap streams through it
     const char* lay = getenv("BMPC_LAYOUT");
     const int slot_major = lay ? atoi(lay) : 1;
-    std::vector<double> work(pipe_workspace_doubles(cap, N, slot_major));
-    pipe_carve(A, work.data(), cap, N, slot_major);
-    std::vector<InstState> st(cap);
-    std::vector<int> l_eval(cap), l_step(cap), l_trial(cap), l_evn(cap), l_trn(cap), l_done(cap), l_admit(cap), l_curv(cap), srcv(cap), cnt(NCNT, 0), tbl(3 * HREC);
-    build_scatter_table(tbl.data());
-    A.st = st.data();
-    A.L.eval = l_eval.data(); A.L.step = l_step.data(); A.L.trial = l_trial.data();
-    A.L.eval_next = l_evn.data(); A.L.trial_next = l_trn.data(); A.L.cnt = cnt.data();
-    A.L.done = l_done.data(); A.L.admit = l_admit.data(); A.L.curv = l_curv.data(); A.src = srcv.data();
-    A.tbl = tbl.data();
-    std::vector<double> lds(std::max<size_t>(std::max<size_t>(pair_lds_doubles(N, true), trial_lds_doubles(N, 4)), RIC_LDS_DOUBLES) + 64);
-    const int n0 = cap;
-    const int nb_inst = (cap + 63) / 64, nw = waves_for(N, cap);
-    cnt[0] = n0; cnt[6] = n0; cnt[9] = n0;
-    launch(nb_inst, [&](int blk, int l) { k_init_inst_body(A, blk * 64 + l); });
-    launch(nw, [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
-    launch(nb_inst, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
-    k_pool_reset_body(A, false);
+    Rig R(B, cap, slot_major, SolverOpts{N, dt, tol, max_iter, hess, hess_switch, mu_init, kappa_mu, theta_mu, kappa_eps, mu_floor_k, dw0, inertia_err, ls_alpha_mem, inertia, stall_n, gn_backoff, slack_reset, trial_repeats},
+          x0, lbx, ubx, p);
+    PipeArgs& A = R.A;
+    std::vector<int>& cnt = R.cnt;
+    double* const lds = R.lds.data();
+    A.x = x; A.f = f; A.viol = viol; A.g = g; A.iters = iters; A.status = status;
+    R.init();
     auto retire = [&]() {        // bmpc_pipe_launch_retire
-        launch(waves_for(N, cnt[8]), [&](int blk, int l) { k_out_body(A, blk, l, lds.data()); });
+        launch(waves_for(N, cnt[8]), [&](int blk, int l) { k_out_body(A, blk, l, lds); });
         launch((cnt[8] + 63) / 64, [&](int blk, int l) { k_fin_body(A, blk * 64 + l); });
         launch((cnt[8] + 63) / 64, [&](int blk, int l) { k_admit_body(A, blk * 64 + l); });
-        launch(waves_for(N, cnt[9]), [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
+        launch(waves_for(N, cnt[9]), [&](int blk, int l) { k_init_body(A, blk, l, lds); });
         launch((cnt[9] + 63) / 64, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
         k_pool_reset_body(A, true);
     };
@@ -98,34 +162,20 @@ extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int he
         retire();
         if (cnt[7] >= B) break;
         if (verbose) printf("step %d: n_eval %d n_trial %d finished %d retired %d next row %d\n", steps, cnt[0], cnt[2], cnt[5], cnt[7], cnt[6]);
-        launch(waves_for(N, cnt[0]), [&](int blk, int l) { k_points_body(A, blk, l, lds.data()); });
-        launch(waves_for(N, cnt[0]), [&](int blk, int l) { k_pose_body(A, blk, l, lds.data()); });
-        if (getenv("BMPC_EMU_EVAL_SPLIT") && atoi(getenv("BMPC_EMU_EVAL_SPLIT"))) {      // the tail regime's two-wavefront k_eval on the GPU
-            launch(waves_for(N, cnt[0]), [&](int blk, int l) { k_eval_body<2>(A, blk, l, lds.data()); });
-            launch(waves_for(N, cnt[0]), [&](int blk, int l) { k_eval_body<1>(A, blk, l, lds.data()); });
-        } else
-        launch(waves_for(N, cnt[0]), [&](int blk, int l) { k_eval_body<0>(A, blk, l, lds.data()); });
-        launch(waves_for(N, cnt[10]), [&](int blk, int l) { k_curv_body(A, blk, l, lds.data()); });
-        if (getenv("BMPC_EMU_RIC_SPEC") && atoi(getenv("BMPC_EMU_RIC_SPEC"))) {      // the speculative pair (the deep tail's kernels on the GPU)
-            A.natt = 3;
-            launch(cnt[0] * A.natt, [&](int blk, int l) { k_ric_att_body<EMU_RIC_NT, false>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
-            launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT, false, true>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
-        } else
-        launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
-        launch(cnt[1], [&](int blk, int l) { k_fwd_body(A, blk, l, lds.data()); });
-        launch(waves_for(N, cnt[1]), [&](int blk, int l) { k_step_body(A, blk, l, lds.data()); });
-        if (getenv("BMPC_EMU_TRIAL_SPEC") && atoi(getenv("BMPC_EMU_TRIAL_SPEC")) && slot_major)      // the tail regime's line search on the GPU
-            launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_spec_body(A, blk, l, lds.data()); }, 64 * TRIAL_SPEC);
+        R.eval(waves_for(N, cnt[0]), env_on("BMPC_EMU_EVAL_SPLIT"));
+        R.direction(env_on("BMPC_EMU_RIC_SPEC"));
+        if (env_on("BMPC_EMU_TRIAL_SPEC") && slot_major)      // the tail regime's line search on the GPU
+            launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_spec_body(A, blk, l, lds); }, 64 * TRIAL_SPEC);
         else
-        launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_body_t<EMU_TRIAL_NW>(A, blk, l, lds.data()); }, 64 * EMU_TRIAL_NW);
+            launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_body_t<EMU_TRIAL_NW>(A, blk, l, lds); }, 64 * EMU_TRIAL_NW);
         k_rotate_body(A);
         std::swap(A.L.eval, A.L.eval_next);
         std::swap(A.L.trial, A.L.trial_next);
     }
     if (lam_g && lam_x) {
         A.lam_g = lam_g; A.lam_x = lam_x;
-        launch(nw, [&](int blk, int l) { k_mult_body(A, blk, l, lds.data()); });
-        launch(nb_inst, [&](int blk, int l) { k_mult_sweep_body(A, blk * 64 + l); });
+        launch(R.nw, [&](int blk, int l) { k_mult_body(A, blk, l, lds); });
+        launch(R.nb_inst, [&](int blk, int l) { k_mult_sweep_body(A, blk * 64 + l); });
     }
     return steps;
 }
@@ -138,48 +188,13 @@ extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int he
 // H [B][N-1][41][41] (k_set_rows_body, k_stage_matrix_body: bmpc_stage_matrix.hpp, the bodies of bmpc_debug_stage_matrices).
 extern "C" int emu_stage_matrices(int N, double dt, int B, const double* w, const double* lbx, const double* ubx, const double* p,
                                   const double* t, const double* z, const double* lam_pi, int split, double* H) {
-    RobotConst rc;
-    fill_robot_const(rc);
-    PipeArgs A;
-    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
-    A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
-    A.o = SolverOpts{N, dt, 1e-5, 100, 2, 1.0, 0.1, 0.1, 2.0, 1000.0, 1e4, 1e-4, 1e-2, 0.0, 2, 8, 2, 1, 9};
-    A.rc = &rc;
-    A.x0 = w; A.lbx = lbx; A.ubx = ubx; A.p = p;
-    std::vector<double> xo((size_t)B * (44 * N + 6)), fo(B), vo(B);
-    std::vector<int> ito(B), sto(B);
-    A.x = xo.data(); A.f = fo.data(); A.viol = vo.data(); A.g = nullptr; A.iters = ito.data(); A.status = sto.data();
-    const int cap = B;
-    std::vector<double> work(pipe_workspace_doubles(cap, N, 1));
-    pipe_carve(A, work.data(), cap, N, 1);
-    std::vector<InstState> st(cap);
-    std::vector<int> l_eval(cap), l_step(cap), l_trial(cap), l_evn(cap), l_trn(cap), l_done(cap), l_admit(cap), l_curv(cap), srcv(cap), cnt(NCNT, 0), tbl(3 * HREC);
-    build_scatter_table(tbl.data());
-    A.st = st.data();
-    A.L.eval = l_eval.data(); A.L.step = l_step.data(); A.L.trial = l_trial.data();
-    A.L.eval_next = l_evn.data(); A.L.trial_next = l_trn.data(); A.L.cnt = cnt.data();
-    A.L.done = l_done.data(); A.L.admit = l_admit.data(); A.L.curv = l_curv.data(); A.src = srcv.data();
-    A.tbl = tbl.data();
-    std::vector<double> lds(std::max<size_t>(std::max<size_t>(pair_lds_doubles(N, true), trial_lds_doubles(N, 4)), RIC_LDS_DOUBLES) + 64);
-    const int nb_inst = (cap + 63) / 64, nw = waves_for(N, cap);
-    cnt[0] = cap; cnt[6] = cap; cnt[9] = cap;
-    launch(nb_inst, [&](int blk, int l) { k_init_inst_body(A, blk * 64 + l); });
-    launch(nw, [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
-    launch(nb_inst, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
-    k_pool_reset_body(A, false);
-    const size_t nset = (size_t)B * (N - 1) * NSLOT;
-    launch((int)((nset + 63) / 64), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z); });
-    launch(nw, [&](int blk, int l) { k_points_body(A, blk, l, lds.data()); });
-    launch(nw, [&](int blk, int l) { k_pose_body(A, blk, l, lds.data()); });
-    if (split) {
-        launch(nw, [&](int blk, int l) { k_eval_body<2>(A, blk, l, lds.data()); });
-        launch(nw, [&](int blk, int l) { k_eval_body<1>(A, blk, l, lds.data()); });
-    } else
-        launch(nw, [&](int blk, int l) { k_eval_body<0>(A, blk, l, lds.data()); });
-    if (cnt[10] != B) return -1;            // every instance is in the curvature list
-    launch(waves_for(N, cnt[10]), [&](int blk, int l) { k_curv_body(A, blk, l, lds.data()); });
+    Rig R(B, B, 1, default_opts(N, dt), w, lbx, ubx, p);
+    R.own_outputs();
+    R.init();
+    R.set_rows(t, z);
+    if (!R.eval(R.nw, split != 0, B)) return -1;            // every instance is in the curvature list
     launch(B, [&](int b, int lane) {
-        k_stage_matrix_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&A), b, lane, lds.data(), lam_pi, H);
+        k_stage_matrix_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&R.A), b, lane, R.lds.data(), lam_pi, H);
     }, EMU_RIC_NT);
     return 0;
 }
@@ -191,49 +206,12 @@ extern "C" int emu_stage_matrices(int N, double dt, int B, const double* w, cons
 extern "C" int emu_newton_step(int N, double dt_, int B, const double* w, const double* lbx, const double* ubx, const double* p,
                                const double* t, const double* z, const int* mode, int variant, double* dzeta, double* dt, double* dz,
                                double* state) {
-    RobotConst rc;
-    fill_robot_const(rc);
-    PipeArgs A;
-    A.B = B; A.N = N; A.natt = 0; A.pad0_ = 0;
-    A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
-    A.o = SolverOpts{N, dt_, 1e-5, 100, 2, 1.0, 0.1, 0.1, 2.0, 1000.0, 1e4, 1e-4, 1e-2, 0.0, 2, 8, 2, 1, 9};
-    A.rc = &rc;
-    A.x0 = w; A.lbx = lbx; A.ubx = ubx; A.p = p;
-    std::vector<double> xo((size_t)B * (44 * N + 6)), fo(B), vo(B);
-    std::vector<int> ito(B), sto(B);
-    A.x = xo.data(); A.f = fo.data(); A.viol = vo.data(); A.g = nullptr; A.iters = ito.data(); A.status = sto.data();
-    const int cap = B;
-    std::vector<double> work(pipe_workspace_doubles(cap, N, 1));
-    pipe_carve(A, work.data(), cap, N, 1);
-    std::vector<InstState> st(cap);
-    std::vector<int> l_eval(cap), l_step(cap), l_trial(cap), l_evn(cap), l_trn(cap), l_done(cap), l_admit(cap), l_curv(cap), srcv(cap), cnt(NCNT, 0), tbl(3 * HREC);
-    build_scatter_table(tbl.data());
-    A.st = st.data();
-    A.L.eval = l_eval.data(); A.L.step = l_step.data(); A.L.trial = l_trial.data();
-    A.L.eval_next = l_evn.data(); A.L.trial_next = l_trn.data(); A.L.cnt = cnt.data();
-    A.L.done = l_done.data(); A.L.admit = l_admit.data(); A.L.curv = l_curv.data(); A.src = srcv.data();
-    A.tbl = tbl.data();
-    std::vector<double> lds(std::max<size_t>(std::max<size_t>(pair_lds_doubles(N, true), trial_lds_doubles(N, 4)), RIC_LDS_DOUBLES) + 64);
-    const int nb_inst = (cap + 63) / 64, nw = waves_for(N, cap);
-    cnt[0] = cap; cnt[6] = cap; cnt[9] = cap;
-    launch(nb_inst, [&](int blk, int l) { k_init_inst_body(A, blk * 64 + l); });
-    launch(nw, [&](int blk, int l) { k_init_body(A, blk, l, lds.data()); });
-    launch(nb_inst, [&](int blk, int l) { k_init_fin_body(A, blk * 64 + l); });
-    k_pool_reset_body(A, false);
-    const size_t nset = (size_t)B * (N - 1) * NSLOT;
-    launch((int)((nset + 63) / 64), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z, mode); });
-    launch(nw, [&](int blk, int l) { k_points_body(A, blk, l, lds.data()); });
-    launch(nw, [&](int blk, int l) { k_pose_body(A, blk, l, lds.data()); });
-    launch(nw, [&](int blk, int l) { k_eval_body<0>(A, blk, l, lds.data()); });
-    launch(waves_for(N, cnt[10]), [&](int blk, int l) { k_curv_body(A, blk, l, lds.data()); });
-    if (variant == 1) {
-        A.natt = 3;
-        launch(cnt[0] * A.natt, [&](int blk, int l) { k_ric_att_body<EMU_RIC_NT, false>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
-        launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT, false, true>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
-    } else
-        launch(cnt[0], [&](int blk, int l) { k_ric_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&A), blk, l, lds.data()); }, EMU_RIC_NT);
-    launch(cnt[1], [&](int blk, int l) { k_fwd_body(A, blk, l, lds.data()); });
-    launch(waves_for(N, cnt[1]), [&](int blk, int l) { k_step_body(A, blk, l, lds.data()); });
-    launch((int)((nset + 63) / 64), [&](int blk, int l) { k_newton_out_body(A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
+    Rig R(B, B, 1, default_opts(N, dt_), w, lbx, ubx, p);
+    R.own_outputs();
+    R.init();
+    R.set_rows(t, z, mode);
+    R.eval(R.nw, false);
+    R.direction(variant == 1);
+    launch((int)((R.nset() + 63) / 64), [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
     return 0;
 }

@@ -64,3 +64,43 @@ def test_throughput_variant_meets_the_dense_solve(N, D, profile, seed):
     for a in out:
         assert np.array_equal(a, rep(a[:D]), equal_nan=True), "copies of one problem at other positions of the batch differ"
     NS.check_case(bt, profile, *(a[:D] for a in out), O, f"HIP kernels, throughput variant, N={N} B={B} ({profile})")
+
+
+def test_entries_of_different_kinds_leave_nothing_behind_on_a_handle():
+    """Solves and the two test entries share the builder of the argument block and the seed of the pool (bmpc_capi.hip: pipe_args,
+    pipe_seed).  One handle, N = 4, B = 5 (one ragged wavefront holding several instances): solve, newton_step, stage_matrices,
+    solve, newton_step.  Repeats of a kind are bitwise equal, and equal to what a fresh handle returns when that kind of call is
+    its first (np.array_equal; bit patterns for newton_step) -- the same kernels run on the same inputs in slots 0 .. B-1.  Directly after a test entry the multipliers of "the
+    last solve" are refused (its iterates are gone from the workspace) and the output buffers stay untouched."""
+    import torch
+    N, B = 4, 5
+    bt = NS.make_batch(N, B, 11, "a")
+    lam_pi = np.random.default_rng(12).normal(size=(B, N, 3))
+    solve = lambda h: h.solve_batch(bt["x0"], bt["lbx"], bt["ubx"], bt["p"])
+    stage = lambda h: h.stage_matrices(bt["x0"], bt["lbx"], bt["ubx"], bt["p"], bt["TS"], bt["ZS"], lam_pi)
+    same_solve = lambda a, b: all(np.array_equal(a[k], b[k]) for k in ("x", "f", "viol", "iters", "status"))
+    # dt and dz carry the NaN that bmpc_k_dbg_set_rows plants in the slots no row uses, and a NaN is not equal to itself: the
+    # newton_step results are compared bit pattern by bit pattern (stricter than np.array_equal where that can hold at all)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint64)
+    same = lambda a, b: all(u.shape == v.shape and np.array_equal(bits(u), bits(v)) for u, v in zip(a, b))
+    h = _handle(N)
+    lg = torch.full((B, h.n_g), -7.0, dtype=torch.float64, device="cuda:0"); lx = torch.full((B, h.n_w), -7.0, dtype=torch.float64, device="cuda:0")
+
+    def refused():
+        with pytest.raises(RuntimeError, match=r"\(1\).*no finished solve of this batch size"):
+            h.multipliers_dev(B, lg.data_ptr(), lx.data_ptr())
+        assert bool((lg == -7.0).all()) and bool((lx == -7.0).all()), "a refused request wrote multipliers"
+
+    s1 = solve(h)
+    n1 = _run(h, bt); refused()
+    m1 = stage(h); refused()
+    s2 = solve(h)
+    h.multipliers_dev(B, lg.data_ptr(), lx.data_ptr())      # (after a solve they are there)
+    assert bool((lg != -7.0).any())
+    lg.fill_(-7.0); lx.fill_(-7.0)
+    n2 = _run(h, bt); refused()
+    assert same_solve(s1, s2), "the second solve differs from the first: a test entry left something on the handle"
+    assert same(n1, n2), "the second newton_step differs from the first: a solve left something on the handle"
+    assert same_solve(s1, solve(_handle(N))), "solve differs from a fresh handle's"
+    assert same(n1, _run(_handle(N), bt)), "newton_step after a solve differs from a fresh handle's first call"
+    assert np.array_equal(m1, stage(_handle(N))), "stage_matrices after a solve and a newton_step differs from a fresh handle's first call"
