@@ -77,7 +77,7 @@ extern "C" int bmpc_create(const bmpc_opts* o, bmpc_handle** out) {
         bmpc_pipe_build_table(tbl.data());
         HIPCHK(h, hipMalloc((void**)&h->d_pipe_tbl, tbl.size() * sizeof(int)));
         HIPCHK(h, hipMemcpy(h->d_pipe_tbl, tbl.data(), tbl.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(h, hipHostMalloc((void**)&h->h_cnt, 2 * NCNT * sizeof(int)));
+        HIPCHK(h, hipHostMalloc((void**)&h->h_cnt, NCNT * sizeof(int)));
     }
     HIPCHK(h, hipStreamCreate(&h->stream));
     HIPCHK(h, hipEventCreate(&h->ev0));
@@ -112,8 +112,7 @@ extern "C" void bmpc_destroy(bmpc_handle* h) {
                     h->d_pipe, h->d_pipe_st, h->d_pipe_lists, h->d_pipe_tbl, h->d_lam_g, h->d_lam_x};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->h_cnt) (void)hipHostFree(h->h_cnt);
-    for (hipEvent_t e : {h->ev0, h->ev1, h->ev_wait, h->ev_fork, h->ev_join_f, h->ev_join_b}) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t s : {h->st_fast, h->st_bulk}) if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : {h->ev0, h->ev1, h->ev_wait}) if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -180,10 +179,10 @@ extern "C" int bmpc_gbounds(const bmpc_handle* h, double* lbg, double* ubg) {
 // ------------------------------------------------------------------------------------------
 // workspace + launch sequence
 // ------------------------------------------------------------------------------------------
-// The work lists of one lane (pipe_solve) in its block of d_pipe_lists: 8 lists and the slot -> row map of `cap` ints each, then the
-// NCNT counters.  Returns the slot -> row map (both lanes work on the same slots: only the bulk lane's map is used).
-static size_t lane_list_ints(int cap) { return 9 * (size_t)cap + NCNT; }
-static int* lane_carve(ListsT<0>& L, int* base, int cap) {
+// The work lists of pipe_solve in d_pipe_lists: 8 lists and the slot -> row map of `cap` ints each, then the NCNT counters.  Returns
+// the slot -> row map.
+static size_t pipe_list_ints(int cap) { return 9 * (size_t)cap + NCNT; }
+static int* pipe_lists_carve(ListsT<0>& L, int* base, int cap) {
     const size_t c = (size_t)cap;
     L.eval = base; L.step = base + c; L.trial = base + 2 * c; L.eval_next = base + 3 * c; L.trial_next = base + 4 * c;
     L.done = base + 5 * c; L.admit = base + 6 * c; L.curv = base + 8 * c; L.cnt = base + 9 * c;
@@ -204,7 +203,7 @@ static int pipe_ensure(bmpc_handle* h, int B) {
     const size_t n = pipe_workspace_doubles(cap, h->o.N, h->slot_major);
     HIPCHK(h, hipMalloc((void**)&h->d_pipe, n * sizeof(double)));
     HIPCHK(h, hipMalloc((void**)&h->d_pipe_st, (size_t)cap * bmpc_pipe_state_bytes()));
-    HIPCHK(h, hipMalloc((void**)&h->d_pipe_lists, 2 * lane_list_ints(cap) * sizeof(int)));       // bulk lane, fast lane
+    HIPCHK(h, hipMalloc((void**)&h->d_pipe_lists, pipe_list_ints(cap) * sizeof(int)));
     h->pipe_cap = cap;
     return 0;
 }
@@ -228,35 +227,6 @@ static void ric_collect(bmpc_handle* h) {        // the stream is idle: every re
     h->ric_pending = 0;
 }
 
-// Two-lane closed loop (pipe_solve with a retire hook and priority flags): streams of the lanes.  reserved_cus > 0: the bulk lane's
-// stream is masked off that many CUs and the fast lane's stream runs on them alone (fast_all: on every CU) -- the fast lane's
-// small grids never queue behind the bulk kernels' workgroups; reserved_cus == 0: the bulk lane stays on the caller's stream, the
-// fast lane gets a stream of the highest priority.
-static int lanes_ensure(bmpc_handle* h, int reserved_cus, int fast_all) {
-    if (h->lane_cfg[0] && h->lane_cfg[1] == reserved_cus && h->lane_cfg[2] == fast_all) return 0;
-    for (hipStream_t* s : {&h->st_fast, &h->st_bulk}) if (*s) { (void)hipStreamSynchronize(*s); (void)hipStreamDestroy(*s); *s = nullptr; }
-    if (!h->ev_fork) {
-        HIPCHK(h, hipEventCreate(&h->ev_fork));
-        HIPCHK(h, hipEventCreate(&h->ev_join_f));
-        HIPCHK(h, hipEventCreate(&h->ev_join_b));
-    }
-    if (reserved_cus > 0 && reserved_cus < h->n_cu) {
-        const int words = (h->n_cu + 31) / 32;
-        std::vector<uint32_t> fast(words, 0u), bulk(words, 0u);
-        for (int c = 0; c < h->n_cu; c++) {
-            if (c < reserved_cus) fast[c / 32] |= 1u << (c % 32); else bulk[c / 32] |= 1u << (c % 32);
-            if (fast_all) fast[c / 32] |= 1u << (c % 32);
-        }
-        HIPCHK(h, hipExtStreamCreateWithCUMask(&h->st_fast, (uint32_t)words, fast.data()));
-        HIPCHK(h, hipExtStreamCreateWithCUMask(&h->st_bulk, (uint32_t)words, bulk.data()));
-    } else {
-        int lo = 0, hi = 0;
-        HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(h, hipStreamCreateWithPriority(&h->st_fast, hipStreamNonBlocking, hi));
-    }
-    h->lane_cfg[0] = 1; h->lane_cfg[1] = reserved_cus; h->lane_cfg[2] = fast_all;
-    return 0;
-}
 static SolverOpts solver_opts(const bmpc_opts& o) {
     return SolverOpts{o.N, o.dt, o.tol, o.max_iter, o.hess, o.hess_switch, o.mu_init, o.kappa_mu, o.theta_mu, o.kappa_eps,
                       o.mu_floor_k, o.dw0, o.inertia_err, o.ls_alpha_mem, o.inertia, o.stall_n, o.gn_backoff, o.slack_reset, o.trial_repeats};
@@ -271,7 +241,7 @@ static PipeArgsH pipe_args(bmpc_handle* h, int B) {
     A.rc = h->d_rc;
     pipe_carve(A, h->d_pipe, cap, N, h->slot_major);
     A.st = (InstState*)h->d_pipe_st;
-    A.src = lane_carve(A.L, h->d_pipe_lists, cap);
+    A.src = pipe_lists_carve(A.L, h->d_pipe_lists, cap);
     A.tbl = h->d_pipe_tbl;
     A.prof = h->d_prof;
     A.lam_g = nullptr; A.lam_x = nullptr; A.cont = nullptr;
@@ -294,24 +264,21 @@ struct PipeRun {
     bmpc_handle* h;
     int B, cap, n0;                 // rows, slots, slots filled at the start
     hipStream_t st;
-    PipeArgsH A;                    // the (bulk) lane
+    PipeArgsH A;
     bmpc_retire_hook hook; void* hook_ctx;
     int steps = 0, retired = 0;
 };
-// retirement of the (at most n_max) instances of lane AA that finished: outputs, the caller's hook, (re-)admission
-static int retire_lane(PipeRun& R, PipeArgsH& AA, int n_max, int refill, hipStream_t s_) {
+// retirement of the (at most n_max) instances that finished: outputs, the caller's hook, (re-)admission
+static int retire(PipeRun& R, int n_max, int refill) {
     bmpc_handle* h = R.h;
-    HIPCHK(h, bmpc_pipe_launch_retire_out(&AA, n_max, s_));
-    if (R.hook) { if (int r = R.hook(R.hook_ctx, AA.L.done, AA.L.cnt + 8, n_max, (void*)s_)) { h->err = "retire hook failed"; return r; } }
-    HIPCHK(h, bmpc_pipe_launch_retire_admit(&AA, n_max, refill, s_));
+    HIPCHK(h, bmpc_pipe_launch_retire_out(&R.A, n_max, R.st));
+    if (R.hook) { if (int r = R.hook(R.hook_ctx, R.A.L.done, R.A.L.cnt + 8, n_max, (void*)R.st)) { h->err = "retire hook failed"; return r; } }
+    HIPCHK(h, bmpc_pipe_launch_retire_admit(&R.A, n_max, refill, R.st));
     return 0;
 }
-// the counters of lane A (and of lane A1, if there is one: zeros otherwise) come back on st; the stream is idle afterwards, so the
-// event pairs of step_timed are collected too
-static int read_counters(bmpc_handle* h, const PipeArgsH& A, const PipeArgsH* A1, hipStream_t st) {
+// the counters come back on st; the stream is idle afterwards, so the event pairs of step_timed are collected too
+static int read_counters(bmpc_handle* h, const PipeArgsH& A, hipStream_t st) {
     HIPCHK(h, hipMemcpyAsync(h->h_cnt, A.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (A1) HIPCHK(h, hipMemcpyAsync(h->h_cnt + NCNT, A1->L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, st));
-    else for (int i = 0; i < NCNT; i++) h->h_cnt[NCNT + i] = 0;
     if (int r = wait_stream(h, st)) return r;
     ric_collect(h);
     return 0;
@@ -336,11 +303,11 @@ static int drive_batch(PipeRun& R) {
         // every super-step; afterwards they are retired once per burst
         const bool rows_left = streaming && next_row < B;
         for (int i = 0; i < burst; i++, R.steps++) {
-            if (rows_left && i > 0) { if (int r = retire_lane(R, R.A, cap, 1, st)) return r; }
+            if (rows_left && i > 0) { if (int r = retire(R, cap, 1)) return r; }
             HIPCHK(h, step_timed(h, &R.A, rows_left ? cap : n_act, st));
         }
-        if (int r = retire_lane(R, R.A, rows_left ? cap : n_act, rows_left ? 1 : 0, st)) return r;
-        if (int r = read_counters(h, R.A, nullptr, st)) return r;
+        if (int r = retire(R, rows_left ? cap : n_act, rows_left ? 1 : 0)) return r;
+        if (int r = read_counters(h, R.A, st)) return r;
         R.retired = h->h_cnt[7];
         next_row = h->h_cnt[6] < B ? h->h_cnt[6] : B;
         n_act = next_row - R.retired;
@@ -355,78 +322,21 @@ static int drive_batch(PipeRun& R) {
 // the done list) are retired -- outputs, the caller's hook (post-processing, next problem), re-admission -- with grids sized by that
 // count; nothing is launched when nobody finished.  (Round 3 ran the whole retirement sequence before every super-step with grids
 // sized for all rollouts: ~1 ms of empty launches per super-step.)  A finished rollout waits at most one burst for its next problem.
-// TWO LANES (round 4; d_prio and prio_max > 0).  With one lane every live rollout iterates at the cadence of a full super-step
-// (2.5 ms at 4096 x N=30), and the run lasts as long as the slowest rollout's iterations (13 k of them on configs[4]) times that.
-// Here the rollouts that lag behind (d_prio, at most prio_max: set by the caller's hook from the steps they have left) iterate in a
-// lane of their own -- lists and counters of its own over the SAME slots and state -- on a second stream, several super-steps of a
-// few dozen instances per bulk super-step.  Per-instance arithmetic does not depend on the lane, so the log stays bitwise that of
-// the lock-step loop.
-struct Lanes {
-    bool two;
-    PipeArgsH A1;                   // the fast lane's argument block
-    hipStream_t sb, sf;             // streams of the bulk lane and of the fast lane
-};
-// (enqueued before the pool is seeded)
-static int lanes_start(PipeRun& R, Lanes& L, const int* d_prio, int prio_max) {
-    bmpc_handle* h = R.h;
-    L.two = d_prio && prio_max > 0;
-    L.A1 = R.A;
-    L.sb = L.sf = R.st;
-    if (!L.two) return 0;
-    if (int r = lanes_ensure(h, env_int("BMPC_FAST_CUS", 0), env_int("BMPC_FAST_ALL", 0))) return r;
-    L.sf = h->st_fast; if (h->st_bulk) L.sb = h->st_bulk;
-    lane_carve(L.A1.L, h->d_pipe_lists + lane_list_ints(R.cap), R.cap);
-    HIPCHK(h, hipMemsetAsync(L.A1.L.cnt, 0, NCNT * sizeof(int), R.st));
-    return 0;
-}
-static int drive_closed_loop(PipeRun& R, Lanes& L, const int* d_prio, int prio_max) {
+static int drive_closed_loop(PipeRun& R) {
     bmpc_handle* h = R.h;
     const int B = R.B;
-    const hipStream_t st = R.st, sb = L.sb, sf = L.sf;
-    const bool two = L.two;
-    PipeArgsH &A = R.A, &A1 = L.A1;
-    const int lane_burst = env_int("BMPC_FAST_BURST", 4);  // super-steps of the bulk lane per burst
-    const int lane_k = env_int("BMPC_FAST_K", 3);          // super-steps of the fast lane per round
+    const hipStream_t st = R.st;
     int n_act = R.n0;
     while (R.retired < B) {      // (no bound on the super-steps: how long a rollout lasts is the caller's business)
         const int burst = R.steps < 8 ? 8 : 4;
-        if (two && R.steps >= 8) {
-            // deal the live instances out between the lanes; the bulk lane then runs its burst while the fast lane goes through
-            // rounds of its own -- a few super-steps, counters back, retirement of ITS finished rollouts (hook and re-admission on
-            // the fast lane's stream: they touch those rollouts only) -- until the bulk burst has ended
-            const int n1 = n_act < prio_max ? n_act : prio_max;
-            HIPCHK(h, bmpc_pipe_launch_pick(&A, &A1, d_prio, n_act, st));
-            HIPCHK(h, hipEventRecord(h->ev_fork, st));
-            HIPCHK(h, hipStreamWaitEvent(sf, h->ev_fork, 0));
-            if (sb != st) HIPCHK(h, hipStreamWaitEvent(sb, h->ev_fork, 0));
-            for (int i = 0; i < lane_burst; i++, R.steps++) HIPCHK(h, step_timed(h, &A, n_act, sb));
-            HIPCHK(h, hipEventRecord(h->ev_join_b, sb));
-            h->lane_stats[0] += 1; h->lane_stats[2] += lane_burst;
-            for (int round = 0;; round++) {
-                for (int i = 0; i < lane_k; i++) HIPCHK(h, bmpc_pipe_launch_step(&A1, n1, sf, nullptr, nullptr, nullptr));
-                HIPCHK(h, hipMemcpyAsync(h->h_cnt + NCNT, A1.L.cnt, NCNT * sizeof(int), hipMemcpyDeviceToHost, sf));
-                if (int r = wait_stream(h, sf)) return r;
-                const int live1 = h->h_cnt[NCNT + 0] + h->h_cnt[NCNT + 2], nd1 = h->h_cnt[NCNT + 8];
-                h->lane_stats[1] += lane_k; h->lane_stats[3] += live1 + nd1; h->lane_stats[6] += 1;
-                const hipError_t q = hipEventQuery(h->ev_join_b);
-                if (q != hipErrorNotReady) { HIPCHK(h, q); break; }          // the bulk burst is over: join (what the fast lane finished last is retired below)
-                if (live1 + nd1 == 0) break;                                  // nobody in the fast lane
-                if (nd1 > 0) { if (int r = retire_lane(R, A1, nd1, 1, sf)) return r; }
-            }
-            HIPCHK(h, hipEventRecord(h->ev_join_f, sf));
-            HIPCHK(h, hipStreamWaitEvent(st, h->ev_join_f, 0));
-            if (sb != st) HIPCHK(h, hipStreamWaitEvent(st, h->ev_join_b, 0));
-        } else {
-            for (int i = 0; i < burst; i++, R.steps++) HIPCHK(h, step_timed(h, &A, n_act, st));
-        }
-        if (int r = read_counters(h, A, two ? &A1 : nullptr, st)) return r;
-        const int n_done = h->h_cnt[8], n_done1 = h->h_cnt[NCNT + 8];
-        if (n_done > 0) { if (int r = retire_lane(R, A, n_done, 1, st)) return r; }
-        if (n_done1 > 0) { if (int r = retire_lane(R, A1, n_done1, 1, st)) return r; }
-        R.retired = h->h_cnt[7] + h->h_cnt[NCNT + 7];      // rows whose rollout has ended (counted by k_admit: one burst behind)
-        if (n_done + n_done1 > 0 && R.retired + n_done + n_done1 >= B) {      // possibly the last ones: their retirement decides whether anybody goes on
-            if (int r = read_counters(h, A, two ? &A1 : nullptr, st)) return r;
-            R.retired = h->h_cnt[7] + h->h_cnt[NCNT + 7];
+        for (int i = 0; i < burst; i++, R.steps++) HIPCHK(h, step_timed(h, &R.A, n_act, st));
+        if (int r = read_counters(h, R.A, st)) return r;
+        const int n_done = h->h_cnt[8];
+        if (n_done > 0) { if (int r = retire(R, n_done, 1)) return r; }
+        R.retired = h->h_cnt[7];      // rows whose rollout has ended (counted by k_admit: one burst behind)
+        if (n_done > 0 && R.retired + n_done >= B) {      // possibly the last ones: their retirement decides whether anybody goes on
+            if (int r = read_counters(h, R.A, st)) return r;
+            R.retired = h->h_cnt[7];
         }
         n_act = B - R.retired;
         h->n_active.store(B - R.retired);
@@ -437,7 +347,7 @@ static int drive_closed_loop(PipeRun& R, Lanes& L, const int* d_prio, int prio_m
 static int pipe_solve(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx,
                       const double* d_p, double* d_x, double* d_g, double* d_f, int* d_iters, int* d_status,
                       double* d_viol, hipStream_t st, bmpc_retire_hook hook = nullptr, void* hook_ctx = nullptr,
-                      const int* d_cont = nullptr, const int* d_prio = nullptr, int prio_max = 0) {
+                      const int* d_cont = nullptr) {
     WEDGED_FAIL(h);
     int rc = pipe_ensure(h, B);
     if (rc) return rc;
@@ -447,20 +357,14 @@ static int pipe_solve(bmpc_handle* h, int B, const double* d_x0, const double* d
     A.x0 = d_x0; A.lbx = d_lbx; A.ubx = d_ubx; A.p = d_p;
     A.x = d_x; A.f = d_f; A.viol = d_viol; A.g = d_g; A.iters = d_iters; A.status = d_status;
     A.cont = d_cont;
-    Lanes L;
-    if (hook) {
-        if (B > cap) { h->err = "closed-loop solve: more rollouts than workspace slots"; return 1; }
-        if (int r = lanes_start(R, L, d_prio, prio_max)) return r;
-        for (double& v : h->lane_stats) v = 0;
-    }
+    if (hook && B > cap) { h->err = "closed-loop solve: more rollouts than workspace slots"; return 1; }
     if (int r = pipe_seed(h, A, R.n0, st, h->ev0)) return r;
     h->n_active.store(B);
     h->ric_pending = 0; h->ric_ms[0] = h->ric_ms[1] = 0; h->ric_launches[0] = h->ric_launches[1] = 0;
     h->ric_full_n = R.n0; h->ric_full[0] = h->ric_full[1] = h->ric_full[2] = 0;
-    if (int r = hook ? drive_closed_loop(R, L, d_prio, prio_max) : drive_batch(R)) return r;
-    const bool two = hook && L.two;
+    if (int r = hook ? drive_closed_loop(R) : drive_batch(R)) return r;
     h->last_steps = R.steps;
-    h->ric_sweeps[0] = h->h_cnt[11] + (two ? h->h_cnt[NCNT + 11] : 0); h->ric_sweeps[1] = h->h_cnt[12] + (two ? h->h_cnt[NCNT + 12] : 0);
+    h->ric_sweeps[0] = h->h_cnt[11]; h->ric_sweeps[1] = h->h_cnt[12];
     HIPCHK(h, hipEventRecord(h->ev1, st));
     // the outputs are complete and the per-handle workspace is free when the call returns (the drivers synchronised)
     if (int r = wait_stream(h, st)) return r;
@@ -489,20 +393,13 @@ extern "C" int bmpc_solve_dev(bmpc_handle* h, int B, const double* d_x0, const d
 // (bmpc_internal.hpp; called by bmpc_loop.hip)
 extern "C" int bmpc_solve_dev_hooked(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx,
                                      const double* d_p, double* d_x, double* d_f, int* d_iters, int* d_status, double* d_viol,
-                                     void* stream, bmpc_retire_hook hook, void* hook_ctx, const int* d_cont,
-                                     const int* d_prio, int prio_max) {
+                                     void* stream, bmpc_retire_hook hook, void* hook_ctx, const int* d_cont) {
     if (!h || B <= 0 || !hook || !d_cont) return 1;
     int wrc = bmpc_wait(h);
     if (wrc) return wrc;
     BUSY_OR_FAIL(h, "bmpc_loop_run_async");
     HIPCHK(h, hipSetDevice(h->o.device));
-    return pipe_solve(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, nullptr, d_f, d_iters, d_status, d_viol, (hipStream_t)stream, hook, hook_ctx, d_cont, d_prio, prio_max);
-}
-// lane statistics of the last two-lane hooked solve (tools/closed_loop_device.py): see bmpc_handle::lane_stats
-extern "C" int bmpc_debug_lane_stats(bmpc_handle* h, double* out8) {
-    if (!h || !out8) return 1;
-    for (int i = 0; i < 8; i++) out8[i] = h->lane_stats[i];
-    return 0;
+    return pipe_solve(h, B, d_x0, d_lbx, d_ubx, d_p, d_x, nullptr, d_f, d_iters, d_status, d_viol, (hipStream_t)stream, hook, hook_ctx, d_cont);
 }
 
 // Asynchronous form of bmpc_solve_dev: returns at once; the data-dependent launch sequence is driven by

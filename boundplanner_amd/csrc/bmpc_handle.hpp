@@ -25,16 +25,10 @@ struct bmpc_handle {
     int slot_major = env_int("BMPC_LAYOUT", 1);
     double* d_pipe = nullptr;      // one slab: SoA iterate/row arrays, stage records, gains, partials
     void* d_pipe_st = nullptr;     // InstState[cap]
-    int* d_pipe_lists = nullptr;   // 8 lists + the slot -> row map of cap ints each + NCNT counters; then the same block again for
-                                   // the fast lane of the closed loop without lock step (pipe_solve)
+    int* d_pipe_lists = nullptr;   // 8 lists + the slot -> row map of cap ints each + NCNT counters
     int* d_pipe_tbl = nullptr;     // scatter table of the stage record
-    int* h_cnt = nullptr;          // pinned host copy of the counters (2 x NCNT: bulk lane, fast lane)
+    int* h_cnt = nullptr;          // pinned host copy of the NCNT counters
     int cnt_seed[bmpc::NCNT] = {0};   // source of the counter upload that seeds the pool (pipe_seed): outlives the enqueued copy
-    // closed loop without lock step, two lanes: streams of the fast lane / of the bulk lane (null: the caller's stream), fork / join events
-    hipStream_t st_fast = nullptr, st_bulk = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join_f = nullptr, ev_join_b = nullptr;
-    int lane_cfg[4] = {0, 0, 0, 0};         // [0] 1 = streams exist; what they were created for: [1] reserved CUs [2] fast lane on all CUs
-    double lane_stats[8] = {0};    // last hooked solve: [0] bursts [1] fast super-steps [2] bulk super-steps [3] sum of the fast lane's instance counts at its round ends [6] fast-lane rounds
     int last_steps = 0;
     bmpc::PipeArgsH last_args;           // arguments of the most recent pipeline solve (its final iterate stays in the workspace)
     bool last_valid = false;

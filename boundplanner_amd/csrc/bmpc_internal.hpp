@@ -39,7 +39,6 @@ hipError_t bmpc_pipe_launch_init(const bmpc::PipeArgsH* A, int n0, hipStream_t s
 hipError_t bmpc_pipe_launch_retire_out(const bmpc::PipeArgsH* A, int n_max, hipStream_t st);
 hipError_t bmpc_pipe_launch_retire_admit(const bmpc::PipeArgsH* A, int n_max, int refill, hipStream_t st);
 hipError_t bmpc_pipe_launch_step(bmpc::PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat);
-hipError_t bmpc_pipe_launch_pick(bmpc::PipeArgsH* A0, bmpc::PipeArgsH* A1, const int* prio, int n_max, hipStream_t st);
 hipError_t bmpc_pipe_launch_mult(const bmpc::PipeArgsH* A, hipStream_t st);
 hipError_t bmpc_pipe_launch_stage_matrices(const bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
                                            double* d_H, hipStream_t st);
@@ -59,5 +58,5 @@ typedef int (*bmpc_retire_hook)(void* ctx, const int* d_done, const int* d_n_don
 // place by `hook`; a row is solved again while d_cont[row] != 0.
 int bmpc_solve_dev_hooked(bmpc_handle* h, int B, const double* d_x0, const double* d_lbx, const double* d_ubx, const double* d_p,
                           double* d_x, double* d_f, int* d_iters, int* d_status, double* d_viol, void* stream, bmpc_retire_hook hook,
-                          void* hook_ctx, const int* d_cont, const int* d_prio, int prio_max);
+                          void* hook_ctx, const int* d_cont);
 }

@@ -1448,15 +1448,10 @@ BMPC_KBODY void k_trial_body_t(const PipeArgs& A, int wave, int tid, LDSD* lds_p
         if constexpr (NW == 1) trial_part<WR_ALL>(A, pg, b, k, pi, live, live && round == 0, alpha, flip, R);
         else {
             TrialPart Q;
-#ifdef BMPC_TRIAL_ONLY      // (register-need experiments: one part only)
-            Q.thr = 0; Q.lp = 1; Q.le = 0; Q.th = 0; Q.f = 0;
-            if (role == 0) trial_part<BMPC_TRIAL_ONLY>(A, pg, b, k, pi, live, live && round == 0, alpha, flip, Q);
-#else
             if (role == 0) trial_part<WR_POSE>(A, pg, b, k, pi, live, live && round == 0, alpha, flip, Q);
             else if (role == 1) trial_part<WR_BOX>(A, pg, b, k, pi, live, live && round == 0, alpha, flip, Q);
             else if (role == 2) trial_part<WR_PT0>(A, pg, b, k, pi, live, live && round == 0, alpha, flip, Q);
             else trial_part<WR_PT1>(A, pg, b, k, pi, live, live && round == 0, alpha, flip, Q);
-#endif
             LDSD* c = comb + (size_t)(role * 64 + lane) * TRIAL_COMB;
             c[0] = Q.thr; c[1] = Q.lp; c[2] = (double)Q.le;
             if (role == 0) { c[3] = Q.th; c[4] = Q.f; }

@@ -13,44 +13,26 @@
 
 using namespace bmpc;
 
-// waves per SIMD the register allocator must leave room for (latency hiding vs spills)
-#ifndef BMPC_PAIR_WPS
-#define BMPC_PAIR_WPS 1
-#endif
-#ifndef BMPC_EVAL_WPS
-#define BMPC_EVAL_WPS BMPC_PAIR_WPS
-#endif
 #ifndef BMPC_TRIAL_NW
 #define BMPC_TRIAL_NW 1      // wavefronts per group of pairs in k_trial: 1 = one walks all rows, 4 = one part of the walk each (measured, not kept: EXPERIMENTS.md)
-#endif
-#ifndef BMPC_TRIAL_WPS
-#define BMPC_TRIAL_WPS (BMPC_TRIAL_NW == 4 ? 2 : BMPC_PAIR_WPS)
-#endif
-#ifndef BMPC_STEP_WPS
-#define BMPC_STEP_WPS BMPC_PAIR_WPS
-#endif
-#ifndef BMPC_POINTS_WPS
-#define BMPC_POINTS_WPS BMPC_PAIR_WPS
-#endif
-#ifndef BMPC_RIC_WPS
-#define BMPC_RIC_WPS 1
 #endif
 
 // the launch argument is the host view of the argument block; device code reads it through the
 // layout-identical view whose pointers are global-address-space qualified
 #define DV(H) (*reinterpret_cast<const PipeArgs*>(&(H)))
 
-// thread-per-pair kernels: one wavefront per workgroup, floor(64/(N-1)) instances per wavefront
+// thread-per-pair kernels: one wavefront per workgroup, floor(64/(N-1)) instances per wavefront; compiled for one wavefront per SIMD
+// (the second launch bound: the allocator may use the whole register file -- two wavefronts per SIMD spill, EXPERIMENTS.md)
 __global__ __launch_bounds__(64) void bmpc_k_init_inst(PipeArgsH H) { k_init_inst_body(DV(H), blockIdx.x * 64 + threadIdx.x); }
 // dynamic LDS of the thread-per-pair kernels: [emitter tile (k_eval, k_curv)] [staged parameter vectors]
 extern __shared__ __attribute__((aligned(16))) double bmpc_dyn_lds[];
-__global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_init(PipeArgsH H) { k_init_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
-__global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_pose(PipeArgsH H) { k_pose_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
-__global__ __launch_bounds__(64, BMPC_EVAL_WPS) void bmpc_k_eval(PipeArgsH H) {
+__global__ __launch_bounds__(64, 1) void bmpc_k_init(PipeArgsH H) { k_init_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_pose(PipeArgsH H) { k_pose_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_eval(PipeArgsH H) {
     k_eval_body<0>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
 }
-__global__ __launch_bounds__(64, BMPC_POINTS_WPS) void bmpc_k_points(PipeArgsH H) { k_points_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
-__global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_curv(PipeArgsH H) {
+__global__ __launch_bounds__(64, 1) void bmpc_k_points(PipeArgsH H) { k_points_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_curv(PipeArgsH H) {
     __shared__ double lds[EM_DOUBLES + 8];
     k_curv_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)lds);
 }
@@ -59,24 +41,24 @@ __global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_curv(PipeArgsH H) {
 // run one body, the rest the other.  Same work in the bulk regime, two launches fewer; in the straggler tail, where a launch costs
 // its single-thread latency, the two bodies run side by side (k_points 39 + k_pose 41 us -> 41, k_eval 113 + k_curv ~50 -> 113).
 // BMPC_SPLIT_LAUNCHES=1 in the environment keeps the four launches (per-kernel profiles).
-__global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_points_pose(PipeArgsH H, int nw) {
+__global__ __launch_bounds__(64, 1) void bmpc_k_points_pose(PipeArgsH H, int nw) {
     if ((int)blockIdx.x < nw) k_points_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
     else k_pose_body(DV(H), (int)blockIdx.x - nw, threadIdx.x, (LDSD*)bmpc_dyn_lds);
 }
-__global__ __launch_bounds__(64, BMPC_EVAL_WPS) void bmpc_k_eval_curv(PipeArgsH H, int nw) {
+__global__ __launch_bounds__(64, 1) void bmpc_k_eval_curv(PipeArgsH H, int nw) {
     if ((int)blockIdx.x < nw) k_eval_body<0>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
     else k_curv_body(DV(H), (int)blockIdx.x - nw, threadIdx.x, (LDSD*)bmpc_dyn_lds);
 }
 // k_eval as two wavefronts side by side (up to BMPC_EVAL_SPLIT_WGS groups of pairs: always, by default) -- everything but the chained block /
 // the chained block alone (bmpc_pair_kernels.hpp, k_eval_body) -- beside k_curv
-__global__ __launch_bounds__(64, BMPC_EVAL_WPS) void bmpc_k_eval_curv_split(PipeArgsH H, int nw) {
+__global__ __launch_bounds__(64, 1) void bmpc_k_eval_curv_split(PipeArgsH H, int nw) {
     if ((int)blockIdx.x < nw) k_eval_body<1>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
     else if ((int)blockIdx.x < 2 * nw) k_eval_body<2>(DV(H), (int)blockIdx.x - nw, threadIdx.x, (LDSD*)bmpc_dyn_lds);
     else k_curv_body(DV(H), (int)blockIdx.x - 2 * nw, threadIdx.x, (LDSD*)bmpc_dyn_lds);
 }
 // (the two bodies as kernels of their own: per-kernel profiles, BMPC_SPLIT_LAUNCHES=1)
-__global__ __launch_bounds__(64, BMPC_EVAL_WPS) void bmpc_k_eval_main(PipeArgsH H) { k_eval_body<1>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
-__global__ __launch_bounds__(64, BMPC_EVAL_WPS) void bmpc_k_eval_chain(PipeArgsH H) { k_eval_body<2>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_eval_main(PipeArgsH H) { k_eval_body<1>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_eval_chain(PipeArgsH H) { k_eval_body<2>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
 #ifndef BMPC_EVAL_SPLIT_WGS
 // groups of pairs up to which bmpc_k_eval_curv_split replaces bmpc_k_eval_curv (0 = never).  Always: built for the latency of the tail
 // regime (a third of k_eval's arithmetic beside the rest), the two lighter bodies also beat the one-wavefront kernel in the bulk regime
@@ -125,11 +107,11 @@ __global__ __launch_bounds__(64) void bmpc_k_fwd(PipeArgsH H) {
     __shared__ __attribute__((aligned(16))) double lds[FW_LDS_DOUBLES];
     k_fwd_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)lds);
 }
-__global__ __launch_bounds__(64, BMPC_STEP_WPS) void bmpc_k_step(PipeArgsH H) { k_step_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_step(PipeArgsH H) { k_step_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
 __global__ __launch_bounds__(64) void bmpc_k_init_fin(PipeArgsH H) { k_init_fin_body(DV(H), blockIdx.x * 64 + threadIdx.x); }
 __global__ __launch_bounds__(64) void bmpc_k_admit(PipeArgsH H) { k_admit_body(DV(H), blockIdx.x * 64 + threadIdx.x); }
 __global__ void bmpc_k_pool_reset(PipeArgsH H, int done_too) { if (threadIdx.x == 0 && blockIdx.x == 0) k_pool_reset_body(DV(H), done_too != 0); }
-__global__ __launch_bounds__(64 * BMPC_TRIAL_NW, BMPC_TRIAL_WPS) void bmpc_k_trial(PipeArgsH H) {
+__global__ __launch_bounds__(64 * BMPC_TRIAL_NW, BMPC_TRIAL_NW == 4 ? 2 : 1) void bmpc_k_trial(PipeArgsH H) {
     k_trial_body_t<BMPC_TRIAL_NW>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
 }
 // the line search of the tail regime: four step lengths side by side, one wavefront (one SIMD) each (bmpc_pair_kernels.hpp)
@@ -140,29 +122,10 @@ __global__ __launch_bounds__(64 * TRIAL_SPEC, 1) void bmpc_k_trial_spec(PipeArgs
 #define BMPC_TRIAL_SPEC_WGS 256       // groups of pairs up to which bmpc_k_trial_spec replaces bmpc_k_trial: one workgroup (four SIMDs) per CU (0 = never)
 #endif
 __global__ void bmpc_k_rotate(PipeArgsH H) { if (threadIdx.x == 0 && blockIdx.x == 0) k_rotate_body(DV(H)); }
-__global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_out(PipeArgsH H) { k_out_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
-__global__ __launch_bounds__(64, BMPC_PAIR_WPS) void bmpc_k_mult(PipeArgsH H) { k_mult_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_out(PipeArgsH H) { k_out_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
+__global__ __launch_bounds__(64, 1) void bmpc_k_mult(PipeArgsH H) { k_mult_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds); }
 __global__ __launch_bounds__(64) void bmpc_k_mult_sweep(PipeArgsH H) { k_mult_sweep_body(DV(H), blockIdx.x * 64 + threadIdx.x); }
 __global__ __launch_bounds__(64) void bmpc_k_fin(PipeArgsH H) { k_fin_body(DV(H), blockIdx.x * 64 + threadIdx.x); }
-
-// Closed loop without lock step, two lanes (bmpc_capi.hip, pipe_solve): the live instances -- eval and trial lists of both lanes --
-// are dealt out again between the bulk lane H0 and the fast lane H1 by the priority flag of their row (prio[row] != 0: the
-// rollout lags behind, its instances iterate at the cadence of a nearly empty GPU).  Destination: the *_next lists (empty between
-// super-steps); bmpc_k_rotate of either lane then makes them current.  Per-instance arithmetic does not depend on the lane.
-__global__ __launch_bounds__(64) void bmpc_k_pick(PipeArgsH H0, PipeArgsH H1, const int* prio) {
-    const PipeArgs& A0 = DV(H0);
-    const PipeArgs& A1 = DV(H1);
-    const int e = blockIdx.x * 64 + threadIdx.x;
-    for (int src = 0; src < 4; src++) {
-        const PipeArgs& S = (src & 1) ? A1 : A0;
-        const bool trial = src >= 2;
-        if (e >= S.L.cnt[trial ? 2 : 0]) continue;
-        const int b = (trial ? S.L.trial : S.L.eval)[e];
-        const PipeArgs& T = prio[A0.src[b]] ? A1 : A0;
-        if (trial) { const int pos = BMPC_ATOMIC_INC(T.L.cnt + 4); T.L.trial_next[pos] = b; }
-        else { const int pos = BMPC_ATOMIC_INC(T.L.cnt + 3); T.L.eval_next[pos] = b; }
-    }
-}
 
 #define LAUNCH(kern, nb, nt)                                            \
     do {                                                                \
@@ -234,8 +197,7 @@ static void launch_direction(PipeArgsH* A, int n_act, int nw, hipStream_t st, hi
     if (n_act < spec_below && n_act > 0) {
         // as many attempts per instance as the chip holds at once: up to 512 workgroups with the latency compilation of the sweeps
         // (two per CU), up to 1536 with the throughput compilation (six per CU)
-        static const int natt_env = env_int("BMPC_RIC_NATT", 0);
-        int natt = natt_env > 0 ? natt_env : (n_act * RIC_NATT <= 512 ? RIC_NATT : 1536 / n_act);
+        const int natt = n_act * RIC_NATT <= 512 ? RIC_NATT : 1536 / n_act;
         A->natt = natt < 2 ? 2 : (natt > RIC_NATT ? RIC_NATT : natt);
         if (n_act * A->natt <= 512) LAUNCH(bmpc_k_ric_att, n_act * A->natt, BMPC_RIC_NT);
         else LAUNCH(bmpc_k_ric_att_thr, n_act * A->natt, BMPC_RIC_NT);
@@ -255,9 +217,6 @@ extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t
     const int nw = waves_for(A->N, n_act);
     launch_eval(A, nw, st);
     launch_direction(A, n_act, nw, st, e0, e1, was_lat);
-    // (BMPC_TRIAL_REPEATS in the environment, read once, overrides bmpc_opts.trial_repeats: A/B runs)
-    static const int env_repeats = env_int("BMPC_TRIAL_REPEATS", -1);
-    if (env_repeats >= 0) A->o.trial_repeats = env_repeats;
     // BMPC_TRIAL_SPEC_WGS (read once; 0 = never): up to that many groups of pairs the step lengths of a line search are tried side by side (slot-major layout)
     static const int trial_spec_wgs = env_int("BMPC_TRIAL_SPEC_WGS", BMPC_TRIAL_SPEC_WGS);
     if (nw <= trial_spec_wgs && A->NP == (size_t)(A->N - 1)) LAUNCH_DYN(bmpc_k_trial_spec, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
@@ -265,17 +224,6 @@ extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t
         LAUNCH_DYN(bmpc_k_trial, nw, 64 * BMPC_TRIAL_NW, trial_lds_doubles(A->N, BMPC_TRIAL_NW));      // trial points (+ multiplier update) + filter test, backtracking inside
     LAUNCH(bmpc_k_rotate, 1, 64);
     swap_lists(A);
-    return hipGetLastError();
-}
-
-// two-lane closed loop: deal the (at most n_max) live instances out between the lanes; swaps the double-buffered lists of both
-extern "C" hipError_t bmpc_pipe_launch_pick(PipeArgsH* A0, PipeArgsH* A1, const int* prio, int n_max, hipStream_t st) {
-    if (n_max <= 0) return hipSuccess;
-    hipLaunchKernelGGL(bmpc_k_pick, dim3((n_max + 63) / 64), dim3(64), 0, st, *A0, *A1, prio);
-    for (PipeArgsH* A : {A0, A1}) {
-        hipLaunchKernelGGL(bmpc_k_rotate, dim3(1), dim3(64), 0, st, *A);
-        swap_lists(A);
-    }
     return hipGetLastError();
 }
 

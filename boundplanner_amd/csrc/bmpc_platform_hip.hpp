@@ -39,11 +39,7 @@
 // doubles that live in LDS: address-space-qualified so that every access is a ds_* instruction
 // (generic pointers to __shared__ memory compile to flat_* loads through the vector-memory path)
 typedef __attribute__((address_space(3))) double LDSD;
-#ifdef BMPC_NO_NOINLINE
-#define BMPC_NOINL __device__
-#else
 #define BMPC_NOINL static __device__ __attribute__((noinline))
-#endif
 
 // 16-byte LDS vector access (ds_read_b128 / ds_write_b128) and fast reciprocal square root
 typedef double bmpc_v2d __attribute__((vector_size(16)));

@@ -38,10 +38,7 @@ constexpr int R_MISC_DOUBLES = 32;
 constexpr int R_misc = R_r0 + NX;
 constexpr int R_acc = R_misc + R_MISC_DOUBLES;   // 2 x 48: per-lane |lambda| sums and dual-residual maxima (lanes < 41)
 constexpr int R_park = R_acc + 96;          // 16: uniform scalars parked across the sweep calls
-#ifndef BMPC_RIC_LDS_PAD
-#define BMPC_RIC_LDS_PAD 0      // (experiments: padding that lowers the number of resident workgroups)
-#endif
-constexpr int RIC_LDS_DOUBLES = R_park + 16 + BMPC_RIC_LDS_PAD;
+constexpr int RIC_LDS_DOUBLES = R_park + 16;
 // the gains K (9 x 32) of a stage live from its factorisation to its Schur complement (both in the factor phase): they share the
 // coupling phase's R_Et, R_Y and the record's R_ew (read by the load and coupling phases, rewritten by the next stage's scatter)
 constexpr int R_Kl = R_Et;
@@ -54,7 +51,7 @@ constexpr int R_dy = R_dzeta + ZPAD;        // 48 (forward start: right-hand sid
 static_assert(R_dy + ZPAD <= R_Y + 3 * NZ, "forward-start scratch fits the coupling scratch");
 // 24.8 KB (31.6 KB with P as 32 x 33 and gains of their own, rounds 1-4: five workgroups per CU): SIX workgroups per CU (160 KB of
 // LDS), i.e. 12 wavefronts = 3 per SIMD, which needs <= 168 VGPRs
-#if !defined(BMPC_PROFILE) && BMPC_RIC_LDS_PAD == 0
+#ifndef BMPC_PROFILE
 static_assert(RIC_LDS_DOUBLES * 8 <= 26624, "k_ric LDS: 6 workgroups per CU");
 #endif
 // P[r][c] in the packed lower triangle
@@ -767,14 +764,6 @@ BMPC_INL void ric_stage_adjoint_impl(RicArgs AH, LDSD* lds, int b, int lane, int
     }
 }
 
-template <int NT> BMPC_NOINL void ric_phase_load(RicArgs AH, LDSD* lds, int b, int lane, int k, int hess_mode, const int* tpk) {
-    ric_phase_load_impl<NT>(AH, lds, b, lane, k, hess_mode, tpk);
-}
-template <int NT> BMPC_NOINL void ric_phase_couple(RicArgs AH, LDSD* lds, int lane) { ric_phase_couple_impl<NT>(AH, lds, lane); }
-template <int NT> BMPC_NOINL bool ric_phase_factor(RicArgs AH, LDSD* lds, int b, int lane, int k) {
-    return ric_phase_factor_impl<NT>(AH, lds, b, lane, k);
-}
-
 // SPLIT = true: the three phases are separate functions (230 VGPRs, two wavefronts per SIMD: the throughput variant, used while
 // many instances are alive); SPLIT = false: one body (the whole register file, one wavefront per SIMD, but 19 % less latency
 // per stage: nothing is recomputed at the phase boundaries) for the straggler tail, where latency is all that counts.
@@ -813,11 +802,6 @@ BMPC_NOINL bool ric_backward(RicArgs AH, LDSD* lds, int b, int lane, int hess_mo
         const bool term = (k == N - 1);
         const size_t pi = pair_of(A, b, k);
         if constexpr (SPLIT) {
-#ifdef BMPC_RIC_CALLS
-            ric_phase_load<NT>(AH, lds, b, lane, k, hess_mode, tpk);
-            if (!term) ric_phase_couple<NT>(AH, lds, lane);
-            if (!ric_phase_factor<NT>(AH, lds, b, lane, k)) ok = false;
-#else
             // the phases inline, each on a lane index the compiler cannot relate to the others': the per-lane offsets are
             // recomputed per phase and stage (as with real calls) instead of being hoisted out of the stage loop, and no
             // call sequence / callee-saved registers are involved
@@ -828,7 +812,6 @@ BMPC_NOINL bool ric_backward(RicArgs AH, LDSD* lds, int b, int lane, int hess_mo
             if (!term) ric_phase_couple_impl<NT>(AH, lds, l1);
             BMPC_OPAQUE_I(l2);
             if (!ric_phase_factor_impl<NT>(AH, lds, b, l2, k)) ok = false;
-#endif
         } else {
             ric_phase_load_impl<NT>(AH, lds, b, lane, k, hess_mode, tpk);
             if (!term) ric_phase_couple_impl<NT>(AH, lds, lane);
@@ -931,11 +914,6 @@ BMPC_NOINL bool ric_forward(RicArgs AH, LDSD* lds, int b, int lane) {
 // One wavefront per instance of the step list, 4.5 KB of LDS: all instances are resident together and
 // hide each other's latency (inside k_ric this part ran at 4 instances per CU).
 // ------------------------------------------------------------------------------------------
-#ifndef BMPC_FW_DEPTH
-#define BMPC_FW_DEPTH 1
-#endif
-constexpr int FW_DEPTH = BMPC_FW_DEPTH;
-static_assert(FW_DEPTH == 1, "k_fwd keeps one stage in flight (depth 3 / 5 measured in round 4: no gain)");
 constexpr int FW_kf = 0, FW_ew = FW_kf + 32, FW_rdef = FW_ew + 42, FW_dx = FW_rdef + NX + 6,
               FW_dzeta = FW_dx + NX, FW_part = FW_dzeta + ZPAD, FW_LDS_DOUBLES = FW_part + 40;
 static_assert(NX == 32 && NU == 9, "k_fwd: nine gain rows in four parts of eight columns, one (row, part) per lane");

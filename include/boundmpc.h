@@ -263,10 +263,6 @@ int bmpc_debug_ric_stats(bmpc_handle* h, double* out6);
 /* ... and of those launches of the throughput variant whose grid was the whole batch (the first super-steps of a solve, before anybody
  * has finished: the kernel at full occupancy): {summed durations [ms], launches, instance-iterations}. */
 int bmpc_debug_ric_stats_full(bmpc_handle* h, double* out3);
-/* Measurement: the two lanes of the most recent bmpc_loop_run_async on this handle (see there): {bursts, fast-lane super-steps,
- * bulk-lane super-steps, summed fast-lane instance counts at the ends of its rounds, 0, 0, fast-lane rounds, 0}; all zero when the
- * run had one lane. */
-int bmpc_debug_lane_stats(bmpc_handle* h, double* out8);
 /* Diagnostic: keeps the handle's stream busy for `ms` milliseconds (at most 10 s, then the kernel ends by itself), so that the
  * watchdog (bmpc_opts.watchdog_ms) can be exercised without a kernel that really hangs. */
 int bmpc_debug_spin(bmpc_handle* h, int ms);

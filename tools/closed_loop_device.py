@@ -189,8 +189,6 @@ def run(args, progress=True):
             #         host + A A^T + upload, per loop (each group's loop holds the scenes its own rollouts use)
             out.update(scene_table_bytes=table_bytes, scene_table_install_s=sum(t_install), scene_table_install_s_per_loop_max=max(t_install))
     if args.async_:
-        out["lanes"] = dict(bes[0].lane_stats(), fast_lane_max=int(os.environ.get("BMPC_FAST_LANE", "0")),
-                            reserved_cus=int(os.environ.get("BMPC_FAST_CUS", "0")))
         tot = it.sum(axis=0)
         out["iters_per_rollout_total_quantiles"] = {f"p{q}": float(np.percentile(tot, q)) for q in (50, 75, 90, 95, 98, 99)}
     if args.dump_failing and G == 1:
