@@ -653,6 +653,42 @@ extern "C" int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, c
     });
 }
 
+// one super-step's Newton step and line search of B instances from given points, rows and line-search state
+extern "C" int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                      const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
+                                      double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
+                                      double* zeta1, double* t1, double* z1, double* ls) {
+    const char* refusal = nullptr;
+    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !dzeta || !dt || !dz || !state || !zeta0 || !t0 || !z0 || !zeta1 || !t1 || !z1 || !ls)
+        refusal = "bad argument";
+    else if ((t == nullptr) != (z == nullptr) || (t == nullptr) != (mode == nullptr)) refusal = "t, z and mode are given together or not at all";
+    else if (!t && (plant0 || plant1)) refusal = "line-search state is planted with given rows only";
+    else if (mode) for (int i = 0; i < B; i++) if (mode[i] < 0 || mode[i] > 2) refusal = "mode must be 0, 1 or 2";
+    if (!refusal && h->o.trial_repeats < 9) refusal = "needs a handle whose line search ends inside one launch (trial_repeats >= 9)";
+    std::optional<BusyGuard> busy;
+    if (int rc = debug_prologue(h, B, "bmpc_debug_line_search", refusal, busy)) return rc;
+    int np0 = 0, np1 = 0, nls = 0;
+    bmpc_pipe_ls_sizes(&np0, &np1, &nls);
+    const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT, nz = B * (N - 1) * NZ;
+    double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
+    int *iters = nullptr, *status = nullptr;
+    Staging s;
+    s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
+    s.in(&t, rows); s.in(&z, rows); s.in(&mode, (size_t)B); s.in(&plant0, (size_t)B * np0); s.in(&plant1, (size_t)B * np1);
+    s.out(&dzeta, nz); s.out(&dt, rows); s.out(&dz, rows); s.out(&state, (size_t)B * 12);
+    s.out(&zeta0, nz); s.out(&t0, rows); s.out(&z0, rows); s.out(&zeta1, nz); s.out(&t1, rows); s.out(&z1, rows); s.out(&ls, (size_t)B * nls);
+    s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
+    const hipStream_t st = h->stream;
+    return s.run(h, st, [&]() -> int {
+        PipeArgsH A = pipe_args(h, B);
+        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
+        A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
+        if (int r = pipe_seed(h, A, B, st)) return r;
+        HIPCHK(h, bmpc_pipe_launch_line_search(&A, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0, t0, z0, zeta1, t1, z1, ls, st));
+        return 0;
+    });
+}
+
 // diagnostic / measurement: HIP events around every launch of the Riccati kernel (bmpc_k_ric: the throughput variant, bmpc_k_ric_lat:
 // the latency variant of nearly empty super-steps) on the handle's stream, from the next solve on.  bmpc_debug_ric_stats returns, for
 // the most recent solve, out[0..2] = {summed launch durations in ms, launches, instance-iterations (workgroups that ran)} of

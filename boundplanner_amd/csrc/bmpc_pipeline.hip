@@ -210,6 +210,15 @@ static void launch_direction(PipeArgsH* A, int n_act, int nw, hipStream_t st, hi
     LAUNCH_DYN(bmpc_k_step, nw, 64, pair_lds_doubles(A->N, false));
 }
 
+// the line search of a super-step for nw groups of pairs: trial points (+ multiplier update) + filter test, backtracking inside
+static void launch_trial(const PipeArgsH* A, int nw, hipStream_t st) {
+    // BMPC_TRIAL_SPEC_WGS (read once; 0 = never): up to that many groups of pairs the step lengths of a line search are tried side by side (slot-major layout)
+    static const int trial_spec_wgs = env_int("BMPC_TRIAL_SPEC_WGS", BMPC_TRIAL_SPEC_WGS);
+    if (nw <= trial_spec_wgs && A->NP == (size_t)(A->N - 1)) LAUNCH_DYN(bmpc_k_trial_spec, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
+    else
+        LAUNCH_DYN(bmpc_k_trial, nw, 64 * BMPC_TRIAL_NW, trial_lds_doubles(A->N, BMPC_TRIAL_NW));
+}
+
 // the host's view of the double-buffered lists after bmpc_k_rotate: the *_next lists are the current ones
 static void swap_lists(PipeArgsH* A) { std::swap(A->L.eval, A->L.eval_next); std::swap(A->L.trial, A->L.trial_next); }
 // one super-step for at most n_act active instances; swaps the double-buffered lists in *A
@@ -217,11 +226,7 @@ extern "C" hipError_t bmpc_pipe_launch_step(PipeArgsH* A, int n_act, hipStream_t
     const int nw = waves_for(A->N, n_act);
     launch_eval(A, nw, st);
     launch_direction(A, n_act, nw, st, e0, e1, was_lat);
-    // BMPC_TRIAL_SPEC_WGS (read once; 0 = never): up to that many groups of pairs the step lengths of a line search are tried side by side (slot-major layout)
-    static const int trial_spec_wgs = env_int("BMPC_TRIAL_SPEC_WGS", BMPC_TRIAL_SPEC_WGS);
-    if (nw <= trial_spec_wgs && A->NP == (size_t)(A->N - 1)) LAUNCH_DYN(bmpc_k_trial_spec, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
-    else
-        LAUNCH_DYN(bmpc_k_trial, nw, 64 * BMPC_TRIAL_NW, trial_lds_doubles(A->N, BMPC_TRIAL_NW));      // trial points (+ multiplier update) + filter test, backtracking inside
+    launch_trial(A, nw, st);
     LAUNCH(bmpc_k_rotate, 1, 64);
     swap_lists(A);
     return hipGetLastError();
@@ -270,8 +275,38 @@ extern "C" hipError_t bmpc_pipe_launch_newton_step(PipeArgsH* A, const double* d
     return hipGetLastError();
 }
 
+// test entry bmpc_debug_line_search: the sequence of bmpc_pipe_launch_newton_step (rows and mode overwritten only when rows are
+// given), then the line search exactly as bmpc_pipe_launch_step issues it for B live instances (launch_trial) -- no rotate -- and the
+// copy-out.  Line-search state is planted before the evaluation launches (with a NaN in the copies the trial writes, when rows are
+// given) and after k_step.
+__global__ __launch_bounds__(64) void bmpc_k_dbg_ls_plant(PipeArgsH H, const double* plant, int after_step, int nan_other) {
+    k_ls_plant_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)plant, after_step, nan_other);
+}
+__global__ __launch_bounds__(64) void bmpc_k_dbg_ls_out(PipeArgsH H, double* zeta0, double* t0, double* z0, double* zeta1, double* t1,
+                                                        double* z1, double* ls) {
+    k_ls_out_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GD)zeta0, (GD)t0, (GD)z0, (GD)zeta1, (GD)t1, (GD)z1, (GD)ls);
+}
+extern "C" hipError_t bmpc_pipe_launch_line_search(PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode,
+                                                   const double* d_plant0, const double* d_plant1, double* d_dzeta, double* d_dt,
+                                                   double* d_dz, double* d_state, double* d_zeta0, double* d_t0, double* d_z0,
+                                                   double* d_zeta1, double* d_t1, double* d_z1, double* d_ls, hipStream_t st) {
+    const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
+    const unsigned nb = (unsigned)((nset + 63) / 64);
+    const int nw = waves_for(A->N, A->B);
+    if (d_t) hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3(nb), dim3(64), 0, st, *A, d_t, d_z, d_mode);
+    if (d_t || d_plant0) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d_plant0, 0, d_t ? 1 : 0);
+    launch_eval(A, nw, st);
+    launch_direction(A, A->B, nw, st, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(bmpc_k_dbg_newton_out, dim3(nb), dim3(64), 0, st, *A, d_dzeta, d_dt, d_dz, d_state);
+    if (d_plant1) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d_plant1, 1, 0);
+    launch_trial(A, nw, st);
+    hipLaunchKernelGGL(bmpc_k_dbg_ls_out, dim3(nb), dim3(64), 0, st, *A, d_zeta0, d_t0, d_z0, d_zeta1, d_t1, d_z1, d_ls);
+    return hipGetLastError();
+}
+
 extern "C" void bmpc_pipe_build_table(int* tbl) { build_scatter_table(tbl); }
 extern "C" int bmpc_pipe_hrec(void) { return HREC; }
 extern "C" int bmpc_pipe_krec(void) { return KREC; }
 extern "C" int bmpc_pipe_npart(void) { return NPART; }
+extern "C" void bmpc_pipe_ls_sizes(int* plant0, int* plant1, int* out) { *plant0 = LS_PLANT0; *plant1 = LS_PLANT1; *out = LS_OUT; }
 extern "C" size_t bmpc_pipe_state_bytes(void) { return sizeof(InstState); }

@@ -4,7 +4,9 @@
 // the exact Hessian on; after the product's evaluation kernels have run once, k_stage_matrix_body runs the sweep's own load phase
 // (ric_phase_load_impl) per stage and copies the matrix it leaves in LDS.  tests/test_hessian_pin*.py compare the result with the
 // reference-derived probes of tests/golden/hess_N*.npz.  The second test entry, bmpc_debug_newton_step, shares k_set_rows_body
-// and adds k_newton_out_body, which copies out what the product's own Riccati, forward and row-step kernels left.
+// and adds k_newton_out_body, which copies out what the product's own Riccati, forward and row-step kernels left.  The third,
+// bmpc_debug_line_search, adds k_ls_plant_body (line-search state planted per instance, NaN in the copies the trial writes) and
+// k_ls_out_body (the iterate before and after the search, the line-search state).
 #pragma once
 #include "bmpc_ric_kernel.hpp"
 
@@ -53,6 +55,87 @@ BMPC_INL void k_newton_out_body(const PipeArgs& A, size_t e, GD dzeta, GD dt, GD
         GD q = state + row * 12;
         q[0] = st->it; q[1] = st->state == ST_DONE ? st->status : -1; q[2] = st->mu; q[3] = st->alpha; q[4] = st->ad; q[5] = st->ap;
         q[6] = st->hreg; q[7] = st->hess_mode; q[8] = st->tries; q[9] = st->bt; q[10] = st->err_prev; q[11] = st->stall;
+    }
+}
+
+// Test entry bmpc_debug_line_search (tests/test_line_search*.py).  Doubles per instance of the two planted records and of the
+// returned line-search state:
+//   plant, before the evaluation launches [LS_PLANT0]: f0, th0, ls0, it, filt_mu, nfilt, filt_th[8], filt_phi[8]
+//   plant, after k_step                   [LS_PLANT1]: nfilt, filt_th[8], filt_phi[8], theta_max, theta_min
+//   state                                 [LS_OUT]:    ap, ad, D, phi0, alpha, bt, f0, th0, ls0, nfilt, filt_th[8], filt_phi[8] (NaN beyond nfilt),
+//                                                      theta_max, theta_min, it, flip, hess_mode, state, mu, filt_mu, armijo, 0
+constexpr int LS_PLANT0 = 22, LS_PLANT1 = 19, LS_OUT = 36;
+
+// one thread per (instance row, stage, slot).  plant (may be null): the record of `after_step` (0 / 1) per instance row, a NaN
+// leaves the field as the product made it.  nan_other: a NaN goes into every slot of the copies of t, z and zeta that are NOT the
+// iterate -- the ones k_trial writes the trial point to -- so that a reader can tell what the search wrote.
+BMPC_INL void k_ls_plant_body(const PipeArgs& A, size_t e, GCD plant, int after_step, int nan_other) {
+    const size_t S = (size_t)(A.N - 1);
+    if (e >= (size_t)A.B * S * NSLOT) return;
+    const int b = (int)(e / (S * NSLOT));                 // slot = row: the pool was filled by the init launch (src[b] = b)
+    const int k = (int)((e / NSLOT) % S) + 1, s = (int)(e % NSLOT);
+    const GST st = A.st + b;
+    if (nan_other) {
+        const int flip = st->flip;
+        const size_t dst = (size_t)s * A.NP + pair_of(A, b, k);
+        oth_t(A, flip)[dst] = __builtin_nan("");
+        oth_z(A, flip)[dst] = __builtin_nan("");
+        if (s < NZ) oth_zeta(A, flip)[dst] = __builtin_nan("");
+    }
+    if (!plant || k != 1 || s != 0) return;
+    if (!after_step) {
+        GCD q = plant + (size_t)b * LS_PLANT0;
+        if (q[0] == q[0]) st->f0 = q[0];
+        if (q[1] == q[1]) st->th0 = q[1];
+        if (q[2] == q[2]) st->ls0 = q[2];
+        if (q[3] == q[3]) st->it = (int)q[3];
+        if (q[4] == q[4]) st->filt_mu = q[4];
+        if (q[5] == q[5]) st->nfilt = (int)q[5];
+        for (int j = 0; j < 8; j++) {
+            if (q[6 + j] == q[6 + j]) st->filt_th[j] = q[6 + j];
+            if (q[14 + j] == q[14 + j]) st->filt_phi[j] = q[14 + j];
+        }
+    } else {
+        GCD q = plant + (size_t)b * LS_PLANT1;
+        if (q[0] == q[0]) st->nfilt = (int)q[0];
+        for (int j = 0; j < 8; j++) {
+            if (q[1 + j] == q[1 + j]) st->filt_th[j] = q[1 + j];
+            if (q[9 + j] == q[9 + j]) st->filt_phi[j] = q[9 + j];
+        }
+        if (q[17] == q[17]) st->theta_max = q[17];
+        if (q[18] == q[18]) st->theta_min = q[18];
+    }
+}
+
+// one thread per (instance row, stage, slot), after the trial launch: zeta0 / zeta1 [B][N-1][NZ], t0, z0, t1, z1 [B][N-1][NSLOT]
+// (kernel slots), ls [B][LS_OUT].  An accepted (or forced) trial has flipped the instance's copies: the iterate before the search is
+// the other copy now.  An instance that took no step (finished at entry) returns its iterate as the one before and NaN after.
+BMPC_INL void k_ls_out_body(const PipeArgs& A, size_t e, GD zeta0, GD t0, GD z0, GD zeta1, GD t1, GD z1, GD ls) {
+    const size_t S = (size_t)(A.N - 1);
+    if (e >= (size_t)A.B * S * NSLOT) return;
+    const int b = (int)(e / (S * NSLOT));
+    const int k = (int)((e / NSLOT) % S) + 1, s = (int)(e % NSLOT);
+    const GST st = A.st + b;
+    const size_t row = (size_t)A.src[b], src = (size_t)s * A.NP + pair_of(A, b, k);
+    const bool moved = st->state != ST_DONE;
+    const int now = st->flip, was = moved ? now ^ 1 : now;
+    const size_t o = (row * S + (size_t)(k - 1)) * NSLOT + s;
+    const double nan = __builtin_nan("");
+    t0[o] = cur_t(A, was)[src]; z0[o] = cur_z(A, was)[src];
+    t1[o] = moved ? cur_t(A, now)[src] : nan; z1[o] = moved ? cur_z(A, now)[src] : nan;
+    if (s < NZ) {
+        const size_t oz = (row * S + (size_t)(k - 1)) * NZ + s;
+        zeta0[oz] = cur_zeta(A, was)[src];
+        zeta1[oz] = moved ? cur_zeta(A, now)[src] : nan;
+    }
+    if (k == 1 && s == 0) {
+        GD q = ls + row * LS_OUT;
+        q[0] = st->ap; q[1] = st->ad; q[2] = st->D; q[3] = st->phi0; q[4] = st->alpha; q[5] = st->bt; q[6] = st->f0; q[7] = st->th0;
+        q[8] = st->ls0; q[9] = st->nfilt;
+        // (entries beyond nfilt are no state: whatever an earlier instance of the slot left there -- returned as NaN)
+        for (int j = 0; j < 8; j++) { const bool in = j < st->nfilt; q[10 + j] = in ? st->filt_th[j] : nan; q[18 + j] = in ? st->filt_phi[j] : nan; }
+        q[26] = st->theta_max; q[27] = st->theta_min; q[28] = st->it; q[29] = st->flip; q[30] = st->hess_mode; q[31] = st->state;
+        q[32] = st->mu; q[33] = st->filt_mu; q[34] = st->armijo; q[35] = 0.0;
     }
 }
 

@@ -254,6 +254,29 @@ int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const dou
  * retries.  Host pointers; B <= workspace slots; the handle must have been created with hess = 2.  rc 1 on misuse. */
 int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
                            const double* t, const double* z, const int* mode, double* dzeta, double* dt, double* dz, double* state);
+/* Test entry: the Newton step AND the filter line search of ONE super-step.  Sequence: that of bmpc_debug_newton_step (init launch,
+ * rows and mode overwritten, the evaluation launches, the Riccati launch, k_fwd, k_step), then the product's trial launch once, in
+ * the variant the number of groups of pairs selects (bmpc_k_trial_spec / bmpc_k_trial); no list rotation.  The handle's
+ * trial_repeats must be the default (>= 9): the whole search ends inside the launch.  t, z, mode as in bmpc_debug_newton_step, or
+ * all three NULL: the rows stay as the init launch made them (the merit pieces are then those of the init launch) and nothing can
+ * be planted.  Line-search state can be planted at two points, per instance, a NaN leaving the field as the product made it:
+ *   plant0 [B][22] (or NULL), before the evaluation launches, together with the rows: f0, th0, ls0 (objective, infeasibility and
+ *     sum log t of the overwritten rows -- the product takes them from the last accepted trial), the iteration counter, filt_mu,
+ *     nfilt, filt_th[8], filt_phi[8].  The line-search start then forms phi0 and applies its own rules to them (theta_max /
+ *     theta_min at iteration 0, filter reset when mu != filt_mu);
+ *   plant1 [B][19] (or NULL), after k_step: nfilt, filt_th[8], filt_phi[8], theta_max, theta_min.
+ * Returned per instance: dzeta, dt, dz, state as from bmpc_debug_newton_step (taken before the trial launch); zeta0 [B][N-1][41]
+ * and t0, z0 [B][N-1][208], the iterate the search started from; zeta1, t1, z1, the iterate after it (with given rows every slot of
+ * the copies the trial writes holds a NaN beforehand: slots the search did not write stay NaN -- except that bmpc_k_trial_spec
+ * copies whole candidate records over when the accepted trial is not the first, slots no row uses included; with t, z == NULL
+ * inactive slots keep t = 1, z = 0; an instance that finished at entry: NaN); ls [B][36]: ap, ad (fraction-to-boundary lengths),
+ * D (merit derivative), phi0, alpha (accepted step length; 1e300: all ten trials rejected, the tenth kept), bt (rejected trials),
+ * f0, th0, ls0 of the new iterate, nfilt, filt_th[8], filt_phi[8] (NaN beyond nfilt), theta_max, theta_min, it, flip, hess_mode, state, mu, filt_mu,
+ * 0, 0.  Host pointers; B <= workspace slots; hess = 2.  rc 1 on misuse. */
+int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                           const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
+                           double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
+                           double* zeta1, double* t1, double* z1, double* ls);
 /* Measurement: from the next solve on, HIP events bracket every launch of the Riccati kernel on the handle's stream
  * (bmpc_debug_time_ric(h, 1)); bmpc_debug_ric_stats then returns for the most recent solve {summed launch durations [ms], launches,
  * instance-iterations} of the throughput variant of that kernel in out6[0..2] and of its latency variant (nearly empty super-steps)

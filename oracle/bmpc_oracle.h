@@ -113,6 +113,11 @@ int bmpc_oracle_newton_system(const bmpc_oracle_opts* o, const double* w, const 
                               const double* t, const double* z, int hess_mode, double mu, double dw, double* H, double* g,
                               double* gdual, double* A, double* B, double* r, double* r0, double* lam, int* nrows, double* h,
                               double* a, double* dzeta);
+/* the oracle's own trial point of a line search: trial slacks after the slack reset and the merit pieces, from the function the solve
+ * loop calls (tests/test_line_search.py; documented in bmpc_solve.c) */
+int bmpc_oracle_trial_point(const bmpc_oracle_opts* o, const double* lbx, const double* ubx, const double* p, const double* zeta0,
+                            const double* dzeta, const double* t0, const double* c, double alpha, double* t1, double* f1,
+                            double* th1, double* ls1);
 int bmpc_oracle_debug_hess(const bmpc_oracle_opts* o, const double* x0, const double* lbx, const double* ubx, const double* p,
                            int k, double zval, double lamval, double* Hout, double* Hfd);
 

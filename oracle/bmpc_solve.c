@@ -898,6 +898,48 @@ static double merit_parts(prob_t* pb, double* f, double* theta, double* logsum) 
     return 0;
 }
 
+/* One trial point of the line search: zeta = zeta0 + alpha dzeta, t = t0 + alpha dt (save: per stage the iterate's zeta [NZ] and
+ * slacks [MAXROWS]; the step in the stages' dzeta, dt_), values at it (eval_stage, mode 1), slack reset, merit pieces.  Called by
+ * the solve loop for every trial and by bmpc_oracle_trial_point. */
+static void trial_point(const bmpc_oracle_opts* o, prob_t* pb, const double* save, double alpha, double* f1, double* th1, double* ls1) {
+    const int N = pb->N;
+    const double dt = pb->dt;
+    for (int k = 1; k < N; k++) {
+        stage_t* s = &pb->st[k];
+        const double* sv = save + k * (NZ + MAXROWS);
+        for (int i = 0; i < NZ; i++) s->zeta[i] = sv[i] + alpha * s->dzeta[i];
+        for (int i = 0; i < s->nrows; i++) s->t[i] = sv[NZ + i] + alpha * s->dt_[i];
+    }
+    if (o->pi_shoot) {
+        /* the rotation-integral state follows its (nonlinear) dynamics exactly at every trial point: pi_{k+1} = pi_k + dt w(q_k, dq_k) */
+        for (int k = 1; k < N - 1; k++) {
+            stage_t* s = &pb->st[k];
+            double y[NZ], J[6][7];
+            bmpc_kin kin;
+            zeta_to_y(pb, s->zeta, y);
+            bmpc_kin_eval(y + Y_Q, &kin);
+            bmpc_kin_jac(&kin, J);
+            for (int a = 0; a < 3; a++) {
+                double om = 0;
+                for (int j = 0; j < 7; j++) om += J[3 + a][j] * y[Y_DQ + j];
+                pb->st[k + 1].zeta[Z_PI + a] = s->zeta[Z_PI + a] + dt * om;
+            }
+        }
+    }
+    for (int i = 0; i < 24; i++) pb->r0[i] = pb->x1fix[i] - pb->st[1].zeta[i];
+    for (int k = N - 1; k >= 1; k--) eval_stage(pb, k, 1);
+    /* slack reset (Byrd, Hribar & Nocedal's interior-point method; KNITRO): a trial slack is never smaller than
+     * the value that closes its row at the trial point, t <- max(t + alpha dt, -h(x + alpha dx)) -- it lowers the
+     * infeasibility theta and the barrier term, and keeps the nonlinearity of the kinematic rows out of theta */
+    if (o->slack_reset)
+        for (int k = 1; k < N; k++) {
+            stage_t* s = &pb->st[k];
+            for (int i = 0; i < s->nrows; i++)
+                if (-s->h[i] > s->t[i]) s->t[i] = -s->h[i];
+        }
+    merit_parts(pb, f1, th1, ls1);
+}
+
 static void setup_problem(const bmpc_oracle_opts* o, prob_t* pbp, const double* x0, const double* lbx,
                           const double* ubx, const double* p, double* pins) {
     int N = o->N;
@@ -1253,41 +1295,8 @@ for (int k = 1; k < N; k++) {
         for (int bt = 0; bt < 10; bt++) {
             ls_bt = bt;
             bmpc_dbg_trials++;
-            for (int k = 1; k < N; k++) {
-                stage_t* s = &pb.st[k];
-                const double* sv = save + k * (NZ + MAXROWS);
-                for (int i = 0; i < NZ; i++) s->zeta[i] = sv[i] + alpha * s->dzeta[i];
-                for (int i = 0; i < s->nrows; i++) s->t[i] = sv[NZ + i] + alpha * s->dt_[i];
-            }
-            if (o->pi_shoot) {
-                /* the rotation-integral state follows its (nonlinear) dynamics exactly at every trial point: pi_{k+1} = pi_k + dt w(q_k, dq_k) */
-                for (int k = 1; k < N - 1; k++) {
-                    stage_t* s = &pb.st[k];
-                    double y[NZ], J[6][7];
-                    bmpc_kin kin;
-                    zeta_to_y(&pb, s->zeta, y);
-                    bmpc_kin_eval(y + Y_Q, &kin);
-                    bmpc_kin_jac(&kin, J);
-                    for (int a = 0; a < 3; a++) {
-                        double om = 0;
-                        for (int j = 0; j < 7; j++) om += J[3 + a][j] * y[Y_DQ + j];
-                        pb.st[k + 1].zeta[Z_PI + a] = s->zeta[Z_PI + a] + dt * om;
-                    }
-                }
-            }
-            for (int i = 0; i < 24; i++) pb.r0[i] = pb.x1fix[i] - pb.st[1].zeta[i];
-            for (int k = N - 1; k >= 1; k--) eval_stage(&pb, k, 1);
-            /* slack reset (Byrd, Hribar & Nocedal's interior-point method; KNITRO): a trial slack is never smaller than
-             * the value that closes its row at the trial point, t <- max(t + alpha dt, -h(x + alpha dx)) -- it lowers the
-             * infeasibility theta and the barrier term, and keeps the nonlinearity of the kinematic rows out of theta */
-            if (o->slack_reset)
-                for (int k = 1; k < N; k++) {
-                    stage_t* s = &pb.st[k];
-                    for (int i = 0; i < s->nrows; i++)
-                        if (-s->h[i] > s->t[i]) s->t[i] = -s->h[i];
-                }
             double f1, th1, ls1;
-            merit_parts(&pb, &f1, &th1, &ls1);
+            trial_point(o, &pb, save, alpha, &f1, &th1, &ls1);
             double phi1 = f1 - mu * ls1;
             int ok = (th1 <= theta_max);
             for (int j = 0; ok && j < nfilt; j++)
@@ -1705,6 +1714,37 @@ int bmpc_oracle_newton_system(const bmpc_oracle_opts* o, const double* w, const 
     }
     free(pb.st); free(pb.lbq); free(pb.ubq);
     return rc;
+}
+
+/* The oracle's own trial point of a line search (tests/test_line_search.py measures with it how far correct double-precision code
+ * lies from the extended-precision reference): iterate zeta0 [N-1][41] with slacks t0 [N-1][MAXROWS] (row order of
+ * bmpc_oracle_stage_rows), step dzeta [N-1][41] and c = t0 + dt [N-1][MAXROWS], step length alpha -> the trial slacks after the
+ * slack reset t1 [N-1][MAXROWS] and the merit pieces f1, th1, ls1 -- trial_point, the function the solve loop calls. */
+int bmpc_oracle_trial_point(const bmpc_oracle_opts* o, const double* lbx, const double* ubx, const double* p, const double* zeta0,
+                            const double* dzeta, const double* t0, const double* c, double alpha, double* t1, double* f1,
+                            double* th1, double* ls1) {
+    prob_t pb;
+    double pins[40];
+    const int N = o->N;
+    double* w0 = (double*)calloc((size_t)44 * N + 6, sizeof(double));
+    setup_problem(o, &pb, w0, lbx, ubx, p, pins);
+    free(w0);
+    for (int k = 1; k < N; k++) memcpy(pb.st[k].zeta, zeta0 + (size_t)(k - 1) * NZ, sizeof(double) * NZ);
+    for (int i = 0; i < 24; i++) pb.r0[i] = pb.x1fix[i] - pb.st[1].zeta[i];
+    for (int k = N - 1; k >= 1; k--) eval_stage(&pb, k, 1);      /* the rows of every stage (their number) */
+    double* save = (double*)calloc((size_t)N * (NZ + MAXROWS), sizeof(double));
+    for (int k = 1; k < N; k++) {
+        stage_t* s = &pb.st[k];
+        const size_t e = (size_t)(k - 1);
+        memcpy(save + k * (NZ + MAXROWS), zeta0 + e * NZ, sizeof(double) * NZ);
+        memcpy(save + k * (NZ + MAXROWS) + NZ, t0 + e * MAXROWS, sizeof(double) * MAXROWS);
+        memcpy(s->dzeta, dzeta + e * NZ, sizeof(double) * NZ);
+        for (int i = 0; i < s->nrows; i++) s->dt_[i] = c[e * MAXROWS + i] - t0[e * MAXROWS + i];
+    }
+    trial_point(o, &pb, save, alpha, f1, th1, ls1);
+    for (int k = 1; k < N; k++) memcpy(t1 + (size_t)(k - 1) * MAXROWS, pb.st[k].t, sizeof(double) * MAXROWS);
+    free(save); free(pb.st); free(pb.lbq); free(pb.ubq);
+    return 0;
 }
 
 /* Analytic stage Lagrangian Hessian (barrier terms left out) against central differences of the stage's own Lagrangian

@@ -132,6 +132,11 @@ struct Rig {
         launch(cnt[1], [&](int blk, int l) { k_fwd_body(A, blk, l, lds.data()); });
         launch(waves_for(N, cnt[1]), [&](int blk, int l) { k_step_body(A, blk, l, lds.data()); });
     }
+    // launch_trial: the line search of the trial list (spec: k_trial_spec_body, the tail regime's kernel on the GPU; slot-major layout)
+    void trial(bool spec) {
+        if (spec) launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_spec_body(A, blk, l, lds.data()); }, 64 * TRIAL_SPEC);
+        else launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_body_t<EMU_TRIAL_NW>(A, blk, l, lds.data()); }, 64 * EMU_TRIAL_NW);
+    }
 };
 
 extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int hess, double hess_switch, double mu_init,
@@ -164,10 +169,7 @@ extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int he
         if (verbose) printf("step %d: n_eval %d n_trial %d finished %d retired %d next row %d\n", steps, cnt[0], cnt[2], cnt[5], cnt[7], cnt[6]);
         R.eval(waves_for(N, cnt[0]), env_on("BMPC_EMU_EVAL_SPLIT"));
         R.direction(env_on("BMPC_EMU_RIC_SPEC"));
-        if (env_on("BMPC_EMU_TRIAL_SPEC") && slot_major)      // the tail regime's line search on the GPU
-            launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_spec_body(A, blk, l, lds); }, 64 * TRIAL_SPEC);
-        else
-            launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_body_t<EMU_TRIAL_NW>(A, blk, l, lds); }, 64 * EMU_TRIAL_NW);
+        R.trial(env_on("BMPC_EMU_TRIAL_SPEC") && slot_major);      // (the tail regime's line search on the GPU)
         k_rotate_body(A);
         std::swap(A.L.eval, A.L.eval_next);
         std::swap(A.L.trial, A.L.trial_next);
@@ -213,5 +215,31 @@ extern "C" int emu_newton_step(int N, double dt_, int B, const double* w, const 
     R.eval(R.nw, false);
     R.direction(variant == 1);
     launch((int)((R.nset() + 63) / 64), [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
+    return 0;
+}
+
+// Newton step and filter line search of one super-step from a given state (tests/test_line_search.py; the bodies of
+// bmpc_debug_line_search): emu_newton_step's sequence -- rows and mode overwritten only when t is given --, line-search state planted
+// before the evaluation bodies (plant0, with a NaN in the copies the trial writes when rows are given) and after k_step (plant1)
+// (k_ls_plant_body; null = nothing), the copy-out of the Newton step, then the trial body ONCE (variant 0: k_trial_body, the kernel
+// bmpc_k_trial; 1: k_trial_spec_body, bmpc_k_trial_spec) with the default trial_repeats -- the search ends inside it --, no
+// k_rotate, and the copy-out k_ls_out_body.
+extern "C" int emu_line_search(int N, double dt_, int B, const double* w, const double* lbx, const double* ubx, const double* p,
+                               const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
+                               int variant, double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
+                               double* zeta1, double* t1, double* z1, double* ls) {
+    if ((t == nullptr) != (z == nullptr) || (t == nullptr) != (mode == nullptr) || (!t && (plant0 || plant1))) return 1;
+    Rig R(B, B, 1, default_opts(N, dt_), w, lbx, ubx, p);
+    R.own_outputs();
+    R.init();
+    const int nb = (int)((R.nset() + 63) / 64);
+    if (t) R.set_rows(t, z, mode);
+    if (t || plant0) launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant0, 0, t ? 1 : 0); });
+    R.eval(R.nw, false);
+    R.direction(false);
+    launch(nb, [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
+    if (plant1) launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant1, 1, 0); });
+    R.trial(variant == 1);
+    launch(nb, [&](int blk, int l) { k_ls_out_body(R.A, (size_t)blk * 64 + l, zeta0, t0, z0, zeta1, t1, z1, ls); });
     return 0;
 }

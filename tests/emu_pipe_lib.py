@@ -77,3 +77,32 @@ def newton_step(N, w, lbx, ubx, p, t, z, mode, dt=0.1, variant=0):
                              P(dzeta), P(dts), P(dzs), P(state))
     assert rc == 0, rc
     return dzeta, dts, dzs, state
+
+
+LS_SHAPES = lambda B, N: dict(dzeta=(B, N - 1, 41), dt=(B, N - 1, 208), dz=(B, N - 1, 208), state=(B, 12), zeta0=(B, N - 1, 41),
+                              t0=(B, N - 1, 208), z0=(B, N - 1, 208), zeta1=(B, N - 1, 41), t1=(B, N - 1, 208), z1=(B, N - 1, 208), ls=(B, 36))
+
+
+def line_search(N, w, lbx, ubx, p, t=None, z=None, mode=None, plant0=None, plant1=None, dt=0.1, variant=1):
+    """emu_line_search: Newton step and filter line search of one super-step of the kernel bodies (the bodies of
+    bmpc_debug_line_search; same arguments and the same dict as HipBoundMPC.line_search); variant 1: k_trial_spec_body (what the
+    GPU runs for a small batch), 0: k_trial_body."""
+    lib = ctypes.CDLL(build())
+    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
+    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
+    B = w.shape[0]
+    P = lambda a: a.ctypes.data_as(_dp) if a is not None else None
+    if t is not None:
+        t, z = (np.ascontiguousarray(a, float) for a in (t, z))
+        mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
+        assert t.shape == z.shape == (B, N - 1, 208)
+    if plant0 is not None:
+        plant0 = np.ascontiguousarray(plant0, float); assert plant0.shape == (B, 22)
+    if plant1 is not None:
+        plant1 = np.ascontiguousarray(plant1, float); assert plant1.shape == (B, 19)
+    out = {k: np.zeros(v) for k, v in LS_SHAPES(B, N).items()}
+    rc = lib.emu_line_search(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z),
+                             mode.ctypes.data_as(_ip) if mode is not None else None, P(plant0), P(plant1), variant,
+                             *(P(out[k]) for k in out))
+    assert rc == 0, rc
+    return out

@@ -187,6 +187,21 @@ def newton_system(N, w, lbx, ubx, p, t, z, hess_mode, mu, dw=0.0, dt=0.1, step=T
     return d
 
 
+def trial_point(N, lbx, ubx, p, zeta0, dzeta, t0, c, alpha, dt=0.1):
+    """The oracle's own trial point (bmpc_oracle_trial_point): (t1 [N-1][216], f1, th1, ls1) for the iterate zeta0 [N-1][41] with
+    slacks t0 [N-1][216] (oracle row order), the step dzeta and c = t0 + dt, and the step length alpha."""
+    lbx, ubx = _boxes(lbx, ubx)
+    lbx, ubx, p, zeta0, dzeta, t0, c = (np.ascontiguousarray(a, float) for a in (lbx, ubx, p, zeta0, dzeta, t0, c))
+    assert zeta0.shape == dzeta.shape == (N - 1, 41) and t0.shape == c.shape == (N - 1, MAXROWS)
+    t1 = np.zeros((N - 1, MAXROWS))
+    f1, th1, ls1 = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    o = _opts(N, dt)
+    rc = lib().bmpc_oracle_trial_point(ctypes.byref(o), _P(lbx), _P(ubx), _P(p), _P(zeta0), _P(dzeta), _P(t0), _P(c), ctypes.c_double(alpha),
+                                       _P(t1), ctypes.byref(f1), ctypes.byref(th1), ctypes.byref(ls1))
+    assert rc == 0
+    return t1, f1.value, th1.value, ls1.value
+
+
 def debug_hess(N, w, lbx, ubx, p, k, zval, lamval, dt=0.1):
     """(analytic, finite-difference) Lagrangian Hessian of stage k without barrier terms (bmpc_oracle_debug_hess)."""
     lbx, ubx = _boxes(lbx, ubx)

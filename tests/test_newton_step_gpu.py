@@ -68,8 +68,8 @@ def test_throughput_variant_meets_the_dense_solve(N, D, profile, seed):
 
 def test_entries_of_different_kinds_leave_nothing_behind_on_a_handle():
     """Solves and the two test entries share the builder of the argument block and the seed of the pool (bmpc_capi.hip: pipe_args,
-    pipe_seed).  One handle, N = 4, B = 5 (one ragged wavefront holding several instances): solve, newton_step, stage_matrices,
-    solve, newton_step.  Repeats of a kind are bitwise equal, and equal to what a fresh handle returns when that kind of call is
+    pipe_seed).  One handle, N = 4, B = 5 (one ragged wavefront holding several instances): solve, newton_step, line_search, stage_matrices,
+    solve, newton_step, line_search.  Repeats of a kind are bitwise equal, and equal to what a fresh handle returns when that kind of call is
     its first (np.array_equal; bit patterns for newton_step) -- the same kernels run on the same inputs in slots 0 .. B-1.  Directly after a test entry the multipliers of "the
     last solve" are refused (its iterates are gone from the workspace) and the output buffers stay untouched."""
     import torch
@@ -91,16 +91,26 @@ def test_entries_of_different_kinds_leave_nothing_behind_on_a_handle():
             h.multipliers_dev(B, lg.data_ptr(), lx.data_ptr())
         assert bool((lg == -7.0).all()) and bool((lx == -7.0).all()), "a refused request wrote multipliers"
 
+    # (t1 only in the slots a row uses: when the accepted trial is not the first, bmpc_k_trial_spec copies whole candidate records over,
+    # and the slots no row uses then hold what the dead gain copies held -- include/boundmpc.h)
+    def search(h):
+        r = h.line_search(bt["x0"], bt["lbx"], bt["ubx"], bt["p"], bt["TS"], bt["ZS"], bt["mode"])
+        return tuple(np.where(bt["ZS"] > 0, v, 0.0) if k == "t1" else v for k, v in r.items())
     s1 = solve(h)
     n1 = _run(h, bt); refused()
+    l1 = search(h); refused()
     m1 = stage(h); refused()
     s2 = solve(h)
     h.multipliers_dev(B, lg.data_ptr(), lx.data_ptr())      # (after a solve they are there)
     assert bool((lg != -7.0).any())
     lg.fill_(-7.0); lx.fill_(-7.0)
     n2 = _run(h, bt); refused()
+    l2 = search(h); refused()
     assert same_solve(s1, s2), "the second solve differs from the first: a test entry left something on the handle"
     assert same(n1, n2), "the second newton_step differs from the first: a solve left something on the handle"
+    assert same(l1, l2), "the second line_search differs from the first: a solve or another entry left something on the handle"
+    assert same(l1, search(_handle(N))), "line_search after a solve differs from a fresh handle's first call"
+    assert same(l1[:4], n1), "line_search returns another Newton step than newton_step"
     assert same_solve(s1, solve(_handle(N))), "solve differs from a fresh handle's"
     assert same(n1, _run(_handle(N), bt)), "newton_step after a solve differs from a fresh handle's first call"
     assert np.array_equal(m1, stage(_handle(N))), "stage_matrices after a solve and a newton_step differs from a fresh handle's first call"
