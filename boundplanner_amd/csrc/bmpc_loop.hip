@@ -133,6 +133,26 @@ __global__ __launch_bounds__(256) void bmpc_loop_k_keep(int R, int N, const doub
     if (S[(size_t)r * LS_SIZE + LS_accept] != 0.0) prev[o] = x[o];
 }
 
+// a reference path for `count` rollouts, one per thread (loop_install_path): the rollouts of a device list with one staged path
+// record each (bmpc_loop_replan), or rollouts first .. first + count - 1 put at rest at q0 on their trivial start-up path
+// (bmpc_loop_init_rollouts: list == nullptr).  Records have the fixed strides of LP_MAXPTS via points.
+__global__ __launch_bounds__(64) void bmpc_loop_k_install(int count, int N, const RobotConst* rc, double* S, int mode, const int* list,
+                                                          int first, const int* n_pts, const double* p_via, const double* r_via,
+                                                          const double* bp1, const double* br1, const double* e_r_bound,
+                                                          const double* a_sets, const double* b_sets, const double* q0,
+                                                          const double* weights) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= count) return;
+    double* s = S + (size_t)(list ? list[e] : first + e) * LS_SIZE;
+    constexpr int NS = LP_MAXPTS - 1;
+    const size_t i = (size_t)e;
+    if (mode == LP_INSTALL_FRESH)
+        loop_install_path(rc, N, s, mode, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, q0 + 7 * i, weights);
+    else
+        loop_install_path(rc, N, s, mode, n_pts[e], p_via + 3 * LP_MAXPTS * i, r_via + 9 * LP_MAXPTS * i, bp1 + 3 * NS * i, br1 + 3 * NS * i,
+                          e_r_bound + 6 * NS * i, a_sets + 45 * NS * i, b_sets + LP_ROWS * NS * i, nullptr, nullptr);
+}
+
 struct bmpc_loop {
     bmpc_handle* h = nullptr;
     int R = 0, N = 0, n_w = 0, dev = 0;
@@ -153,6 +173,9 @@ struct bmpc_loop {
     double* d_rec = nullptr;       // [steps][n_rec][lp_rec_doubles(N)] of the last bmpc_loop_run
     size_t rec_cap = 0, rec_steps = 0;
     int async_nsteps = 0;
+    void* d_inst = nullptr;        // staged arguments of bmpc_loop_replan / bmpc_loop_init_rollouts (grows, never shrinks)
+    size_t inst_cap = 0;
+    float inst_ms = 0.f;           // the last install kernel by the events e0 / e1
     double* async_log = nullptr;
     size_t log_cap = 0;
     hipStream_t st = nullptr;
@@ -222,6 +245,7 @@ extern "C" void bmpc_loop_destroy(bmpc_loop* L) {
     if (L->d_rollout_scene) (void)hipFree(L->d_rollout_scene);
     if (L->d_steps_left) (void)hipFree(L->d_steps_left);
     if (L->d_cont) (void)hipFree(L->d_cont);
+    if (L->d_inst) (void)hipFree(L->d_inst);
     if (L->e0) (void)hipEventDestroy(L->e0);
     if (L->e1) (void)hipEventDestroy(L->e1);
     if (L->h) bmpc_handle_release(L->h);     // a bmpc_destroy deferred because of this loop runs now
@@ -377,6 +401,76 @@ extern "C" int bmpc_loop_set_rollout_scenes(bmpc_loop* L, int first, int count, 
     LCHK(L, hipMemcpy(L->d_rollout_scene + first, scene, (size_t)count * sizeof(int), hipMemcpyHostToDevice));
     return 0;
 }
+
+// ---- reference paths installed on the device (loop_install_path) ---------------------------------------------------------
+// The arguments are checked on the host before anything is enqueued, so an error leaves the device state as it was.  Then, on
+// the loop's stream and therefore after whatever is in flight: the staged copies, one bmpc_loop_k_install, the wait.
+namespace {
+struct InstArg { const void* host; size_t bytes; size_t off; };
+constexpr size_t INST_ALIGN = 256;
+
+int install_run(bmpc_loop* L, int count, int mode, int first, InstArg* a, int n_args) {
+    size_t total = 0;
+    for (int i = 0; i < n_args; i++) { a[i].off = total; total += (a[i].bytes + INST_ALIGN - 1) / INST_ALIGN * INST_ALIGN; }
+    LCHK(L, hipSetDevice(L->dev));      // the calling host thread may be new
+    if (total > L->inst_cap) {          // (every call here waits for its kernel, so the old block is idle)
+        if (L->d_inst) (void)hipFree(L->d_inst);
+        L->d_inst = nullptr; L->inst_cap = 0;
+        LCHK(L, hipMalloc(&L->d_inst, total));
+        L->inst_cap = total;
+    }
+    const char* d = (const char*)L->d_inst;
+    for (int i = 0; i < n_args; i++)
+        LCHK(L, hipMemcpyAsync((void*)(d + a[i].off), a[i].host, a[i].bytes, hipMemcpyHostToDevice, L->st));
+    auto D = [&](int i) { return (const double*)(d + a[i].off); };
+    LCHK(L, hipEventRecord(L->e0, L->st));
+    if (mode == LP_INSTALL_FRESH)
+        hipLaunchKernelGGL(bmpc_loop_k_install, dim3((count + 63) / 64), dim3(64), 0, L->st, count, L->N, L->d_rc, L->d_S, mode, (const int*)nullptr,
+                           first, (const int*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr,
+                           (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, D(0), D(1));
+    else
+        hipLaunchKernelGGL(bmpc_loop_k_install, dim3((count + 63) / 64), dim3(64), 0, L->st, count, L->N, L->d_rc, L->d_S, mode,
+                           (const int*)(d + a[0].off), 0, (const int*)(d + a[1].off), D(2), D(3), D(4), D(5), D(6), D(7), D(8),
+                           (const double*)nullptr, (const double*)nullptr);
+    LCHK(L, hipGetLastError());
+    LCHK(L, hipEventRecord(L->e1, L->st));
+    LCHK(L, hipStreamSynchronize(L->st));
+    LCHK(L, hipEventElapsedTime(&L->inst_ms, L->e0, L->e1));
+    return 0;
+}
+}  // namespace
+
+extern "C" int bmpc_loop_replan(bmpc_loop* L, int count, const int* rollouts, const int* n_pts, const double* p_via, const double* r_via,
+                                const double* bp1, const double* br1, const double* e_r_bound, const double* a_sets, const double* b_sets) {
+    if (!L) return 1;
+    if (count == 0) return 0;
+    if (count < 0 || !rollouts || !n_pts || !p_via || !r_via || !bp1 || !br1 || !e_r_bound || !a_sets || !b_sets) {
+        L->err = "bmpc_loop_replan: bad arguments"; return 1;
+    }
+    std::vector<char> seen((size_t)L->R, 0);
+    for (int i = 0; i < count; i++) {
+        if (rollouts[i] < 0 || rollouts[i] >= L->R) { L->err = "bmpc_loop_replan: rollout index out of range"; return 1; }
+        if (seen[(size_t)rollouts[i]]) { L->err = "bmpc_loop_replan: a rollout is listed twice"; return 1; }
+        seen[(size_t)rollouts[i]] = 1;
+        if (n_pts[i] < 2 || n_pts[i] > LP_MAXPTS) { L->err = "bmpc_loop_replan: a path needs 2 to 8 via points"; return 1; }
+    }
+    const size_t c = (size_t)count, NS = LP_MAXPTS - 1, D = sizeof(double);
+    InstArg a[9] = {{rollouts, c * sizeof(int), 0}, {n_pts, c * sizeof(int), 0}, {p_via, c * 3 * LP_MAXPTS * D, 0}, {r_via, c * 9 * LP_MAXPTS * D, 0},
+                    {bp1, c * 3 * NS * D, 0}, {br1, c * 3 * NS * D, 0}, {e_r_bound, c * 6 * NS * D, 0}, {a_sets, c * 45 * NS * D, 0},
+                    {b_sets, c * LP_ROWS * NS * D, 0}};
+    return install_run(L, count, LP_INSTALL_REPLAN, 0, a, 9);
+}
+
+extern "C" int bmpc_loop_init_rollouts(bmpc_loop* L, int first, int count, const double* q0, const double* weights) {
+    if (!L) return 1;
+    if (count == 0) return 0;
+    if (!range_ok(L, first, count)) return 1;
+    if (!q0 || !weights) { L->err = "bmpc_loop_init_rollouts: bad arguments"; return 1; }
+    InstArg a[2] = {{q0, (size_t)count * 7 * sizeof(double), 0}, {weights, 11 * sizeof(double), 0}};
+    return install_run(L, count, LP_INSTALL_FRESH, first, a, 2);
+}
+
+extern "C" float bmpc_loop_install_ms(const bmpc_loop* L) { return L ? L->inst_ms : 0.f; }
 
 // n rollouts at most: all of them (list == nullptr, n == R) or those of a device list
 static int launch_prepare(bmpc_loop* L, hipStream_t st, int n, const int* list = nullptr, const int* n_list = nullptr) {

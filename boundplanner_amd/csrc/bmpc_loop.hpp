@@ -13,10 +13,12 @@
 //   integrate_joint (first hat interval)     utils/util_functions.py:55-65, jerk_trajectory_casadi.py:78-175
 //   MPCNode.step state advance               BoundMPC/MPCNode.py:106-160
 //   obstacle-free collision sets             BoundPlanner/ConvexSetFinder.py:400-421 (+ util_functions.py:121-135)
-// The plan-time construction (ReferencePath.__init__, BoundMPC.update) stays on the host
-// (boundplanner_amd/reference_path.py, bound_mpc.py) and is serialised into the state vector below by
-// boundplanner_amd/device_loop.py.  Scenes with obstacles need the host collision-set finder and are
-// refused by the device loop.
+//   plan-time construction                   ReferencePath.py:12-157, BoundMPC.py:28-336 (loop_install_path)
+// The plan-time construction (ReferencePath.__init__, BoundMPC.__init__ / update) has two routes into the state
+// vector below: built on the host (boundplanner_amd/reference_path.py, bound_mpc.py) and serialised by
+// boundplanner_amd/device_loop.py pack_state, or written on the device by loop_install_path, which restates
+// exactly that host code.  Scenes with obstacles are handled on the device as well: the per-step collision
+// sets come from the closest-pair pass further down (one shared scene, or one scene per rollout).
 //
 // Written against the platform macros of bmpc_platform_hip.hpp so that tests/emu/emu_loop.cpp can run
 // the identical source on the CPU against the reference's closed-loop trace (test infrastructure only).
@@ -896,6 +898,188 @@ BMPC_DEV void loop_finish(const RobotConst* rc, int N, double dt, double* S, con
         for (int c = 0; c < 6; c++) log[10 + c] = S[LS_p_lie + c];
         for (int j = 0; j < 7; j++) log[16 + j] = S[LS_q + j];
     }
+}
+
+// ---- installing a reference path: ReferencePath.__init__ + BoundMPC.update / __init__ + pack_state -------------------
+// One rollout gets a new via path on the device.  The host code is the specification -- ReferencePath.__init__
+// (boundplanner_amd/reference_path.py), BoundMPC.update / __init__ (bound_mpc.py) and pack_state (device_loop.py) -- and the state
+// vector afterwards is what pack_state would have written, including what looks accidental there: the padded list entries, the
+// in-place normalisation of the dp entries that share an object with entry 0 or 1, the padded dr entries that keep the undivided
+// increment, zeros in every field pack_state does not write.  The lists are built in S itself (no local array indexed by a runtime
+// value); the record is read where the caller staged it.
+constexpr int LP_MAXPTS = 8;     // via points of a path, at most (LP_NL = LP_MAXPTS + LP_S - 1)
+enum LoopInstallMode { LP_INSTALL_REPLAN = 0, LP_INSTALL_FRESH = 1 };
+
+BMPC_INL double lp_norm3(const double* a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
+
+// orthonormal pair around the unit direction d: b1 = the part of `want` orthogonal to d ([1,1,1] when want is parallel to d),
+// b2 = d x b1 (ReferencePath.py:109-150)
+BMPC_INL void lp_basis_pair(const double* d, const double* want, double* b1, double* b2) {
+    double s = d[0] * want[0] + d[1] * want[1] + d[2] * want[2];
+    double b[3] = {want[0] - s * d[0], want[1] - s * d[1], want[2] - s * d[2]};
+    if (lp_norm3(b) < 1e-3) {
+        s = d[0] + d[1] + d[2];
+        for (int c = 0; c < 3; c++) b[c] = 1.0 - s * d[c];
+    }
+    const double nb = lp_norm3(b);
+    for (int c = 0; c < 3; c++) b[c] /= nb;
+    const double x[3] = {d[1] * b[2] - d[2] * b[1], d[2] * b[0] - d[0] * b[2], d[0] * b[1] - d[1] * b[0]};
+    const double nx = lp_norm3(x);
+    for (int c = 0; c < 3; c++) { b1[c] = b[c]; b2[c] = x[c] / nx; }
+}
+
+// rows n_real .. n_real + LP_S - 2 of a list of `w` doubles per row: copies of row n_real - 1
+BMPC_INL void lp_pad_rows(double* list, int w, int n_real) {
+    for (int k = 0; k < LP_S - 1; k++)
+        for (int c = 0; c < w; c++) list[w * (n_real + k) + c] = list[w * (n_real - 1) + c];
+}
+
+// LP_INSTALL_REPLAN: DeviceLoop.replan -- the record is n_pts in 2..8, p_via [n_pts][3], r_via [n_pts][9] row-major,
+//   bp1 / br1 [n_pts-1][3], e_r_bound [n_pts-1][6], a_sets [n_pts-1][15][3], b_sets [n_pts-1][15]; q0 / weights unused.
+//   q, dq, ddq, jerk, v, p_lie, slacks0, error_count, has_prev, weights carry over.
+// LP_INSTALL_FRESH: BatchMPCNode.__init__ + DeviceLoop.set_rollout for the start configuration q0 [7] with weights [11] -- the
+//   rollout at rest on the trivial path [p0, p0]; the record is unused.
+BMPC_DEV void loop_install_path(const RobotConst* rc, int N, double* S, int mode, int n_pts, const double* p_via, const double* r_via,
+                                const double* bp1, const double* br1, const double* e_r_bound, const double* a_sets, const double* b_sets,
+                                const double* q0, const double* weights) {
+    const double PI = 3.141592653589793;
+    const bool fresh = mode == LP_INSTALL_FRESH;
+    if (fresh) {
+        for (int j = 0; j < 7; j++) { S[LS_q + j] = q0[j]; S[LS_dq + j] = 0.0; S[LS_ddq + j] = 0.0; S[LS_jerk + j] = 0.0; }
+        for (int c = 0; c < 6; c++) { S[LS_v + c] = 0.0; S[LS_slacks0 + c] = 0.0; }
+        Kin k;
+        kin_eval(rc, S + LS_q, k);
+        for (int c = 0; c < 3; c++) S[LS_p_lie + c] = k.pee[c];
+        lp_mat_to_rotvec(k.Ree, S + LS_p_lie + 3);
+        S[LS_error_count] = 0.0; S[LS_has_prev] = 0.0;
+        for (int i = 0; i < 11; i++) S[LS_weights + i] = weights[i];
+    } else {
+        S[LS_error_count] = (double)(int)S[LS_error_count];       // (the host carries it as an int)
+        S[LS_has_prev] = (S[LS_has_prev] != 0.0) ? 1.0 : 0.0;
+    }
+    for (int j = 0; j < 7; j++) S[LS_qf + j] = S[LS_q + j];
+    // what neither mode keeps: pack_state starts from zeros
+    for (int i = LS_split; i < LS_error_count; i++) S[i] = 0.0;
+    for (int i = LS_pr_ref; i < LS_weights; i++) S[i] = 0.0;
+    for (int i = LS_dtau; i < LS_SIZE; i++) S[i] = 0.0;
+
+    const int n = fresh ? 2 : n_pts;
+    unsigned same0 = 0u, same1 = 0u;       // bit i: list entry dp[i] is the same host object as dp[0] / dp[1]
+    double phi_sum = 0.0;
+    if (fresh) {
+        for (int i = 0; i < 2 + LP_S - 1; i++)
+            for (int c = 0; c < 3; c++) { S[LS_rp_p + 3 * i + c] = S[LS_p_lie + c]; S[LS_rp_r_tau + 3 * i + c] = S[LS_p_lie + 3 + c]; }
+        for (int i = 0; i < 1 + LP_S - 1; i++) {      // one segment without length or rotation: the defaults of ReferencePath
+            S[LS_rp_drn + 3 * i + 1] = 1.0; S[LS_rp_dp + 3 * i + 1] = 1.0;
+            S[LS_rp_bp1 + 3 * i] = 1.0; S[LS_rp_br1 + 3 * i] = 1.0; S[LS_rp_bp2 + 3 * i + 2] = -1.0; S[LS_rp_br2 + 3 * i + 2] = -1.0;
+            for (int c = 0; c < 6; c++) S[LS_rp_erb + 6 * i + c] = (c < 3 ? 90.0 : -90.0) * PI / 180.0;
+            for (int r = 0; r < LP_ROWS; r++) S[LS_rp_b + LP_ROWS * i + r] = 1.0;
+        }
+    } else {
+        // via points and orientations (ReferencePath.py:43-76); the orientation increments stay undivided for now
+        for (int i = 0; i < n; i++) {
+            for (int c = 0; c < 3; c++) S[LS_rp_p + 3 * i + c] = p_via[3 * i + c];
+            lp_mat_to_rotvec(r_via + 9 * i, S + LS_rp_r_tau + 3 * i);
+        }
+        double ax[3] = {0.0, 1.0, 0.0};
+        for (int i = 1; i < n; i++) {
+            double rT[9], m[9], d[3];
+            lp_mat3T(r_via + 9 * (i - 1), rT);
+            mat3mul(r_via + 9 * i, rT, m);
+            lp_mat_to_rotvec(m, d);
+            const double nrm = lp_norm3(d);
+            if (nrm > 1e-4) {
+                const double a[3] = {d[0] / nrm, d[1] / nrm, d[2] / nrm}, s[3] = {ax[0] + a[0], ax[1] + a[1], ax[2] + a[2]};
+                const double sg = (lp_norm3(s) < 1e-4) ? -1.0 : 1.0;       // keep the projection axis on reversal
+                for (int c = 0; c < 3; c++) ax[c] = sg * a[c];
+            }
+            for (int c = 0; c < 3; c++) {
+                S[LS_rp_dr + 3 * (i - 1) + c] = d[c];
+                S[LS_rp_drn + 3 * (i - 1) + c] = ax[c];
+                S[LS_rp_iw + 3 * i + c] = S[LS_rp_iw + 3 * (i - 1) + c] + d[c];
+            }
+        }
+        // position increments and arc lengths (ReferencePath.py:78-106).  A segment shorter than 1e-3 IS the entry before it on
+        // the host (the same object), the padded entries are the last real one: root = the entry whose object entry i holds
+        int root = 0, root1 = 0;
+        for (int i = 0; i < n - 1; i++) {
+            double d[3] = {p_via[3 * (i + 1)] - p_via[3 * i], p_via[3 * (i + 1) + 1] - p_via[3 * i + 1], p_via[3 * (i + 1) + 2] - p_via[3 * i + 2]};
+            double li = lp_norm3(d);
+            if (li < 1e-3) {
+                for (int c = 0; c < 3; c++) d[c] = (i > 0) ? S[LS_rp_dp + 3 * (i - 1) + c] : (c == 1 ? 1.0 : 0.0);
+                li = lp_norm3(S + LS_rp_dr + 3 * i) / PI;        // a pure rotation gets |dr| / pi of path parameter
+            } else {
+                root = i;
+            }
+            for (int c = 0; c < 3; c++) S[LS_rp_dp + 3 * i + c] = d[c];
+            S[LS_rp_phi + i + 1] = li;
+            phi_sum += li;
+            if (i == 1) root1 = root;
+            if (root == 0) same0 |= 1u << i;
+            if (i >= 1 && root == root1) same1 |= 1u << i;
+        }
+        if (n == 2) root1 = root;            // entry 1 is a padded copy of entry 0
+        for (int k = 0; k < LP_S - 1; k++) {
+            if (root == 0) same0 |= 1u << (n - 1 + k);
+            if (root == root1) same1 |= 1u << (n - 1 + k);
+        }
+        if (root1 == 0) same1 |= 1u;
+        // bases around the position / rotation directions, bounds and sets (ReferencePath.py:109-150, 43-46)
+        for (int i = 0; i < n - 1; i++) {
+            const double* dp = S + LS_rp_dp + 3 * i;
+            const double nd = lp_norm3(dp), dirn[3] = {dp[0] / nd, dp[1] / nd, dp[2] / nd};
+            lp_basis_pair(dirn, bp1 + 3 * i, S + LS_rp_bp1 + 3 * i, S + LS_rp_bp2 + 3 * i);
+            const double drn[3] = {S[LS_rp_drn + 3 * i], S[LS_rp_drn + 3 * i + 1], S[LS_rp_drn + 3 * i + 2]};
+            lp_basis_pair(drn, br1 + 3 * i, S + LS_rp_br1 + 3 * i, S + LS_rp_br2 + 3 * i);
+            for (int c = 0; c < 6; c++) S[LS_rp_erb + 6 * i + c] = e_r_bound[6 * i + c];
+            for (int c = 0; c < 45; c++) S[LS_rp_a + 45 * i + c] = a_sets[45 * i + c];
+            for (int c = 0; c < LP_ROWS; c++) S[LS_rp_b + LP_ROWS * i + c] = b_sets[LP_ROWS * i + c];
+        }
+        // the nr_segs - 1 padded copies of every list; dr is padded BEFORE the division below, so its copies keep the
+        // undivided last increment
+        lp_pad_rows(S + LS_rp_p, 3, n); lp_pad_rows(S + LS_rp_r_tau, 3, n); lp_pad_rows(S + LS_rp_iw, 3, n);
+        lp_pad_rows(S + LS_rp_dr, 3, n - 1); lp_pad_rows(S + LS_rp_drn, 3, n - 1); lp_pad_rows(S + LS_rp_dp, 3, n - 1);
+        lp_pad_rows(S + LS_rp_bp1, 3, n - 1); lp_pad_rows(S + LS_rp_bp2, 3, n - 1); lp_pad_rows(S + LS_rp_br1, 3, n - 1);
+        lp_pad_rows(S + LS_rp_br2, 3, n - 1); lp_pad_rows(S + LS_rp_erb, 6, n - 1); lp_pad_rows(S + LS_rp_a, 45, n - 1);
+        lp_pad_rows(S + LS_rp_b, LP_ROWS, n - 1);
+        // angular velocity per unit path parameter (ReferencePath.py:153-155)
+        for (int i = 0; i < n - 1; i++) {
+            const double ph = S[LS_rp_phi + i + 1];
+            if (ph > 1e-8) for (int c = 0; c < 3; c++) S[LS_rp_dr + 3 * i + c] /= ph;
+        }
+    }
+    for (int k = 0; k < LP_S - 1; k++) S[LS_rp_phi + n + k] = 1.0;
+    S[LS_rp_phi_max] = phi_sum; S[LS_phi_max] = phi_sum;
+    S[LS_rp_num_sectors] = (double)(n - 2);       // rp_sector = rp_phi_bias = 0, phi_switch[0] = phi_bias
+    for (int i = 0; i < LP_S; i++) lp_set_point(S, i);
+    S[LS_split] = 0.0;
+    for (int i = 1; i <= LP_S; i++) S[LS_split + i] = (double)N;
+
+    if (fresh) {      // BoundMPC.__init__: phi_current = dphi_current = 0, iw_ref = 0
+        for (int c = 0; c < 3; c++) S[LS_pr_ref + c] = S[LS_p_lie + 3 + c];
+        return;
+    }
+    // BoundMPC.update normalises dp[0] and dp[1] IN PLACE, after the window was filled: every list entry that is the same object
+    // ends up unit length (twice divided when both are one object), the others keep their length
+    {
+        const double nd = lp_norm3(S + LS_rp_dp);
+        for (int i = 0; i < n + LP_S - 2; i++)
+            if ((same0 >> i) & 1u) for (int c = 0; c < 3; c++) S[LS_rp_dp + 3 * i + c] /= nd;
+    }
+    {
+        const double nd = lp_norm3(S + LS_rp_dp + 3);
+        for (int i = 0; i < n + LP_S - 2; i++)
+            if ((same1 >> i) & 1u) for (int c = 0; c < 3; c++) S[LS_rp_dp + 3 * i + c] /= nd;
+    }
+    double phi_c = 0.0, dphi_c = 0.0;
+    for (int c = 0; c < 3; c++) {
+        phi_c += (S[LS_p_lie + c] - p_via[c]) * S[LS_rp_dp + c];
+        dphi_c += S[LS_v + c] * S[LS_rp_dp + c];
+    }
+    S[LS_phi_current] = phi_c; S[LS_dphi_current] = dphi_c;
+    const double om[3] = {S[LS_rp_dr], S[LS_rp_dr + 1], S[LS_rp_dr + 2]};
+    lp_integrate_rot_ref(S + LS_rp_r_tau, om, 0.0, phi_c, S + LS_pr_ref);
+    for (int c = 0; c < 3; c++) S[LS_iw_ref + c] = S[LS_rp_pd + LP_S * (3 + c)] + phi_c * S[LS_rp_dpd + LP_S * (3 + c)];
 }
 
 // host-side layout lookup for the packer (boundplanner_amd/device_loop.py): offset / count of a state field

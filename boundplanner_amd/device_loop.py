@@ -1,10 +1,12 @@
 """Device-resident closed loop (BASELINE.json configs[4]): R rollouts advanced in lock step on one
 MI355X, every step = prepare kernel -> batched NLP solve -> finish kernel, with the per-rollout state
-(robot state, ReferencePath window, split indices, warm start) living in HBM.  Only the plan-time
-construction runs on the host: `BoundMPC.__init__/update` + `ReferencePath.__init__`
+(robot state, ReferencePath window, split indices, warm start) living in HBM.  The plan-time
+construction has two routes.  On the host: `BoundMPC.__init__/update` + `ReferencePath.__init__`
 (/root/reference/bound_planner/BoundMPC/BoundMPC.py:28-336, ReferencePath/ReferencePath.py:12-157) build
 the Python objects, `pack_state` serialises them into the state vector of
-boundplanner_amd/csrc/bmpc_loop.hpp, and the HIP kernels carry on from there
+boundplanner_amd/csrc/bmpc_loop.hpp (`set_rollout`, `replan` between `download` and `upload`).  On the device:
+`init_rollouts` and `replan_batch` hand start configurations / via paths to the install kernel, which writes the same
+state vectors in HBM (loop_install_path).  Either way the HIP kernels carry on from there
 (BoundMPC.step / compute_return_data / MPCNode.step, BoundMPC.py:388-1040, MPCNode.py:106-160).
 
 No CPU fallback: `DeviceLoop` needs libboundmpc_hip.so and a GPU.  Scene obstacles (polytopes with their vertices, the
@@ -98,6 +100,31 @@ def pack_obstacles(obs_sets, obs_points_sets):
     return A, b, nrows, V, nv
 
 
+MAX_PTS = 8      # LP_MAXPTS of bmpc_loop.hpp: via points of a path
+
+
+def pack_plans(plans):
+    """[(p_via, r_via, bp1, br1, e_r_bound, a_sets, b_sets), ...] as DeviceLoop.replan takes them -> the arrays of
+    bmpc_loop_replan: n_pts [n], p_via [n][8][3], r_via [n][8][9], bp1 / br1 [n][7][3], e_r_bound [n][7][6], a_sets [n][7][15][3],
+    b_sets [n][7][15].  Copies: the caller's lists are left as they are (host ReferencePath appends to them)."""
+    n = len(plans)
+    n_pts = np.zeros(n, np.int32)
+    out = [np.zeros((n, MAX_PTS, 3)), np.zeros((n, MAX_PTS, 9)), np.zeros((n, MAX_PTS - 1, 3)), np.zeros((n, MAX_PTS - 1, 3)),
+           np.zeros((n, MAX_PTS - 1, 6)), np.zeros((n, MAX_PTS - 1, 45)), np.zeros((n, MAX_PTS - 1, 15))]
+    for i, plan in enumerate(plans):
+        k = len(plan[0])
+        if not 2 <= k <= MAX_PTS:
+            raise ValueError(f"plan {i}: {k} via points, the device loop takes 2 to {MAX_PTS}")
+        n_pts[i] = k
+        for j, (lst, arr) in enumerate(zip(plan, out)):
+            want = k if j < 2 else k - 1
+            if len(lst) != want:
+                raise ValueError(f"plan {i}: list {j} has {len(lst)} entries, {want} expected for {k} via points")
+            for e, a in enumerate(lst):
+                arr[i, e] = np.asarray(a, float).reshape(-1)
+    return (n_pts, *out)
+
+
 def state_view(lay, S):
     """dict of named views into one state vector (or a [R, size] array of them)."""
     S = np.asarray(S)
@@ -130,7 +157,7 @@ class DeviceLoop:
             raise RuntimeError(f"bmpc_loop_create failed ({rc}): {msg} -- the device loop has no CPU fallback")
         self.state = np.zeros((self.R, self.lay["_size"]))
         self.prev = np.zeros((self.R, backend.n_w))
-        self.ms_total = self.ms_solve = 0.0
+        self.ms_total = self.ms_solve = self.ms_install = 0.0
 
     def close(self):
         if getattr(self, "_l", None):
@@ -205,6 +232,33 @@ class DeviceLoop:
                    params=Params(n=self.N, dt=self.be.opts.dt, build=False, weights=V["weights"].copy(), nr_segs=mpc.nr_segs))
         self.state[r] = pack_state(self.lay, mpc, q, V["dq"].copy(), V["ddq"].copy(), V["jerk"].copy(), q, V["v"].copy(),
                                    V["p_lie"].copy())
+
+    def replan_batch(self, rollouts, plans):
+        """replan() for many rollouts at once, on the device (bmpc_loop_replan): plans[i] = (p_via, r_via, bp1, br1, e_r_bound,
+        a_sets, b_sets) is the new via path of rollout rollouts[i], tracked from that rollout's current DEVICE state -- p_via[0] is
+        supplied by the caller, as for replan().  Needs no download() / upload() and no host BoundMPC object; the host copy
+        `self.state` is not refreshed (download() does that).  The plans' lists are not modified."""
+        rollouts = np.ascontiguousarray(rollouts, np.int32).reshape(-1)
+        if len(rollouts) != len(plans):
+            raise ValueError("one plan per rollout")
+        n_pts, *arrs = pack_plans(plans)
+        self._chk(self.lib.bmpc_loop_replan(self._l, len(rollouts), rollouts.ctypes.data_as(_ip), n_pts.ctypes.data_as(_ip),
+                                            *[self._P(a) for a in arrs]), "bmpc_loop_replan")
+        self.ms_install = self.lib.bmpc_loop_install_ms(self._l) if len(rollouts) else 0.0
+
+    def init_rollouts(self, q0s, weights=None, first=0):
+        """Rollouts first, first + 1, ... at rest at the start configurations q0s [n, 7], on the trivial start-up path at their own
+        end-effector pose and without a warm start: what BatchMPCNode.__init__ + set_rollout() + upload() give, built on the device
+        (bmpc_loop_init_rollouts).  weights: the 11 MPC weights (default: get_default_params().weights)."""
+        q0s = np.ascontiguousarray(q0s, float).reshape(-1, 7)
+        if weights is None:
+            from .params import get_default_params
+            weights = get_default_params().weights
+        w = np.ascontiguousarray(weights, float).reshape(-1)
+        if w.size != 11:
+            raise ValueError("11 weights expected")
+        self._chk(self.lib.bmpc_loop_init_rollouts(self._l, int(first), len(q0s), self._P(q0s), self._P(w)), "bmpc_loop_init_rollouts")
+        self.ms_install = self.lib.bmpc_loop_install_ms(self._l) if len(q0s) else 0.0
 
     def horizon_points(self, r):
         """End-effector positions of rollout r's last accepted solution, stage by stage: the `p_horizon` argument of

@@ -88,6 +88,7 @@ EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error"
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_set_scenes", "bmpc_loop_set_rollout_scenes", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
+           "bmpc_loop_replan", "bmpc_loop_init_rollouts", "bmpc_loop_install_ms",
            "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev", "bmpc_default_sets_opts", "bmpc_convex_sets", "bmpc_convex_sets_dev"]
 
 _lib = None
@@ -151,6 +152,10 @@ def load_library():
         lib.bmpc_debug_time_ric.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.bmpc_debug_ric_stats.argtypes = [ctypes.c_void_p, _dp]
         lib.bmpc_debug_ric_stats_full.argtypes = [ctypes.c_void_p, _dp]
+        lib.bmpc_loop_replan.argtypes = [ctypes.c_void_p, ctypes.c_int, _ip, _ip] + [_dp] * 7
+        lib.bmpc_loop_init_rollouts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp, _dp]
+        lib.bmpc_loop_install_ms.restype = ctypes.c_float
+        lib.bmpc_loop_install_ms.argtypes = [ctypes.c_void_p]
         lib.bmpc_loop_set_record.argtypes = [ctypes.c_void_p, ctypes.c_int, _ip]
         lib.bmpc_loop_records.argtypes = [ctypes.c_void_p, _dp, ctypes.c_int, _ip]
         lib.bmpc_loop_record_doubles.argtypes = [ctypes.c_int]

@@ -296,9 +296,10 @@ int bmpc_debug_spin(bmpc_handle* h, int ms);
  * call: BoundMPC.step before the solve (BoundMPC.py:388-589), the acceptance test and
  * compute_return_data (BoundMPC.py:604-1040), ReferencePath.update (ReferencePath.py:187-207),
  * MPCNode.step's state advance with integrate_joint (MPCNode.py:106-160, util_functions.py:55-65).
- * Plan-time construction (ReferencePath.__init__, BoundMPC.update) stays with the caller, who
+ * Plan-time construction (ReferencePath.__init__, BoundMPC.__init__ / update) either stays with the caller, who
  * serialises it into the state vector: bmpc_loop_state_doubles() doubles per rollout, fields located by
- * name with bmpc_loop_field() (names = LP_FIELDS of boundplanner_amd/csrc/bmpc_loop.hpp).
+ * name with bmpc_loop_field() (names = LP_FIELDS of boundplanner_amd/csrc/bmpc_loop.hpp) -- or runs on the device as well:
+ * bmpc_loop_init_rollouts / bmpc_loop_replan below.
  * Per-step collision sets (ConvexSetFinder.find_set_collision_avoidance, ConvexSetFinder.py:309-375) are computed on the
  * device too: boxes around the collision points, plus separating halfspaces of the scene obstacles set with
  * bmpc_loop_set_obstacles (one scene, every rollout uses it) or with bmpc_loop_set_scenes / bmpc_loop_set_rollout_scenes (a table of
@@ -339,6 +340,24 @@ int bmpc_loop_set_rollout_scenes(bmpc_loop* l, int first, int count, const int* 
 /* state: [count][state_doubles]; prev: [count][n_w] previous solutions (warm start) or NULL */
 int bmpc_loop_upload(bmpc_loop* l, int first, int count, const double* state, const double* prev);
 int bmpc_loop_download(bmpc_loop* l, int first, int count, double* state, double* prev);
+/* Reference paths installed on the device, one rollout per thread, with the result the host construction + serialisation gives
+ * (boundplanner_amd: ReferencePath.__init__, BoundMPC.update / __init__, device_loop.pack_state) -- no download / upload of states.
+ * bmpc_loop_replan: a new via path for each of `count` rollouts (MPCNode.update_reference, MPCNode.py:82-104), tracked from the
+ *   rollout's CURRENT device state: q, dq, ddq, jerk, v, p_lie, slacks0, error count, warm start and weights carry over, qf = q, the
+ *   path window, split indices and rotation reference start over.  rollouts [count]: indices in any order, each at most once;
+ *   n_pts [count]: via points of path i, 2 .. 8; records with the strides of 8 via points, of which the first n_pts (n_pts - 1) are
+ *   read: p_via [count][8][3], r_via [count][8][9] (rotation matrices, row-major), bp1 / br1 [count][7][3] (desired basis directions
+ *   per segment), e_r_bound [count][7][6] (upper 3, lower 3), a_sets [count][7][15][3], b_sets [count][7][15].
+ * bmpc_loop_init_rollouts: rollouts first .. first+count-1 at rest at q0 [count][7] with the MPC weights [11] (Params.weights), on the
+ *   trivial start-up path at their own end-effector pose (BoundMPC.__init__ as BatchMPCNode calls it), no warm start.
+ * Both enqueue on the loop's stream, after whatever is in flight, and wait.  count = 0 is a no-op.  Misuse (null pointer, rollout index
+ * out of range or listed twice, n_pts outside 2 .. 8) returns 1 with a message in bmpc_loop_last_error, checked on the host before
+ * anything is enqueued: the device state stays as it was.  2: HIP error.  Neither touches the warm-start rows or a rollout that is
+ * not listed.  bmpc_loop_install_ms: HIP-event time of the install kernel of the last successful call of either. */
+int bmpc_loop_replan(bmpc_loop* l, int count, const int* rollouts, const int* n_pts, const double* p_via, const double* r_via,
+                     const double* bp1, const double* br1, const double* e_r_bound, const double* a_sets, const double* b_sets);
+int bmpc_loop_init_rollouts(bmpc_loop* l, int first, int count, const double* q0, const double* weights);
+float bmpc_loop_install_ms(const bmpc_loop* l);
 /* nsteps MPC steps of all rollouts; log: [nsteps][R][log_doubles] or NULL -- per row: iters, status,
  * viol, error_count, dead, phi, phi_max, split_idx[1], sector, switch, p_lie(6), q(7).
  * ms_total: HIP-event time of the whole run on the loop's stream; ms_solve: host time inside the solves */

@@ -43,6 +43,8 @@ def parser():
     ap.add_argument("--diagnose", default=None, help="write a JSON with the classification of the rollouts that did not reach the path end")
     ap.add_argument("--groups", type=int, default=3, help="rollout groups stepped concurrently (own solver handle and stream "
                     "each): the straggler tail of one group's solve overlaps the bulk of another's")
+    ap.add_argument("--device-setup", action="store_true", help="install the start-up path and the first plan of every rollout on the device "
+                    "(DeviceLoop.init_rollouts / replan_batch) instead of building a host BoundMPC object per rollout and uploading its state")
     ap.add_argument("--opt", action="append", default=[], help="solver option key=value (bmpc_opts field), A/B runs")
     return ap
 
@@ -92,7 +94,9 @@ def run(args, progress=True):
     else:
         q_start, q_goal = scenes.sample_start_goal(rng, be.fk, R)
         fs, fg = be.fk(q_start), be.fk(q_goal)
-    seed_objs = BatchMPCNode(be, q_start, params)          # host construction of the R BoundMPC objects (trivial start-up path)
+    # host construction of the R BoundMPC objects (trivial start-up path); with --device-setup the install kernel does it
+    seed_objs = None if args.device_setup else BatchMPCNode(be, q_start, params)
+    ms_install = 0.0
     loops = [DeviceLoop(bes[g], bounds[g + 1] - bounds[g]) for g in range(G)]
     a_ee, b_ee = scenes._box_set([-1.0, -1.0, 0.0], [1.0, 1.0, 1.2])
     for g, loop in enumerate(loops):
@@ -108,6 +112,18 @@ def run(args, progress=True):
             t_install.append(time.perf_counter() - t1)
             n_o = [len(table[i][0]) for i in used]
             table_bytes += sum(n_o) * (8 * (45 + 15 + 225 + 96 + 6) + 12) + 4 * (len(used) + 1) + 4 * len(of) + len(of) * 6 * max(n_o) * 64
+        if args.device_setup:
+            loop.init_rollouts(q_start[bounds[g]:bounds[g + 1]], params.weights)
+            ms_install += loop.ms_install
+            loop.run(1, log=False)                         # the same start-up solve
+            V = loop.download()                            # (only p_lie is read: where the plans start)
+            sets = normalize_set_size([[a_ee, b_ee]], 15)
+            erb = np.array([90, 90, 90, -90, -90, -90]) * np.pi / 180
+            loop.replan_batch(np.arange(bounds[g + 1] - bounds[g]),
+                              [([V["p_lie"][i][:3], fg["ee_pos"][r]], [fs["ee_rot"][r], fg["ee_rot"][r]], [np.array([0.0, 0, 1])],
+                                [np.array([0.0, 0, 1])], [erb], [sets[0][0]], [sets[0][1]]) for i, r in enumerate(range(bounds[g], bounds[g + 1]))])
+            ms_install += loop.ms_install
+            continue
         for i, r in enumerate(range(bounds[g], bounds[g + 1])):
             loop.set_rollout(i, seed_objs.mpcs[r], seed_objs.q[r], seed_objs.dq[r], seed_objs.ddq[r], seed_objs.jerk[r],
                              seed_objs.qf[r], seed_objs.v[r], seed_objs.p_lie[r])
@@ -173,6 +189,9 @@ def run(args, progress=True):
         "solves": int(R * args.steps), "wall_s": wall, "solves_per_s": R * args.steps / wall,
         "gpu_stream_ms_total": ms_total, "host_ms_inside_solves": ms_solve, "ms_per_step": 1e3 * wall / args.steps,
         "plan_time_host_setup_s": t_plan,
+        # how the paths got into the loop: "host" = one BoundMPC object per rollout, serialised and uploaded; "device" = the install
+        # kernel (its HIP-event time, all init_rollouts / replan_batch calls of the setup; None on the host route)
+        "setup": "device" if args.device_setup else "host", "install_kernels_ms": ms_install if args.device_setup else None,
         "iters_mean": float(it.mean()), "iters_p50": float(np.median(it)), "iters_p99": float(np.percentile(it, 99)),
         "iters_first_step_mean": float(it[0].mean()), "fail_frac": float(np.concatenate(fails).mean()), "dead_frac": dead,
         "reached_end_frac": float((reached_at > 0).mean()),
