@@ -548,51 +548,66 @@ BMPC_INL void p17_emit_all(const PipeArgs& A, PGP pg, const RP& rp, const BP& bp
 // Fv (on v; WITHOUT the multiplier of the pi dynamics, which k_ric adds), Fc (on the 6 points)
 // sa, sbq, sbdq, sc1: the chained rank-2 curvature of the sigmoid-weighted error terms, c1 a a^T + b a^T + a b^T with
 // a on q only and b = (bq, bdq, bpi); its q x pi part is emitted by the caller
+//
+// q x q block: third derivatives of the kinematics contracted with forces and dq -- symmetric in (a, bq), so the upper triangle is
+// computed and both halves are emitted from it.  Its entries are evaluated COLUMN BY COLUMN (bq = 6 ... 0), each column on copies of
+// the joint axes and Jacobian columns that are opaque to the compiler (BMPC_PIN).  Left to itself the compiler shares the inner
+// cross products (z_m x Jl_M, z_bq x z_j, z_M x r_c) between all 28 entries of the unrolled nest and keeps them alive throughout,
+// which does not fit the register file; with the copies a column's products are computed when the column is reached and die with it
+// (a few are computed twice).  Every entry is the same sequence of operations on the same values as in one nest over (a, bq): the
+// block is bitwise the same.  (EM: the emitter; a template parameter only so that a test can capture the entries.)
+template <class EM>
 BMPC_INL void curvature_emit(const KinT& K, const double Jl[3][7], const double* dq, const double* Fp, const double* Fv,
-                             const double Fc[6][3], const double* sa, const double* sbq, const double* sbdq, double sc1, Emitter& E) {
+                             const double Fc[6][3], const double* sa, const double* sbq, const double* sbdq, double sc1, EM& E) {
     const int njc[6] = {2, 3, 4, 5, 6, 4};
-    // q x q block: third derivatives of the kinematics contracted with forces and dq -- symmetric in (a, bq), so the upper
-    // triangle is computed and both halves are emitted from it
     double tri[28];
     BMPC_UNROLL
-    for (int a = 0; a < 7; a++)
+    for (int bq = 6; bq >= 0; bq--) {
+        // this column's own copies: nothing of a column is computed before the column before it is finished, nothing is kept for the next
+        double zx[7][3], Jc[3][7];
         BMPC_UNROLL
-        for (int bq = a; bq < 7; bq++) {
+        for (int i = 0; i < 7; i++)
+            BMPC_UNROLL
+            for (int x = 0; x < 3; x++) { zx[i][x] = K.zx[i][x]; Jc[x][i] = Jl[x][i]; BMPC_PIN(zx[i][x]); BMPC_PIN(Jc[x][i]); }
+        BMPC_UNROLL
+        for (int a = 0; a <= bq; a++) {
             const int m = a < bq ? a : bq, M = a < bq ? bq : a;
-            double cM[3] = {Jl[0][M], Jl[1][M], Jl[2][M]}, zc[3];
-            cross3r(K.zx[m], cM, zc);
+            double cM[3] = {Jc[0][M], Jc[1][M], Jc[2][M]}, zc[3];
+            cross3r(zx[m], cM, zc);
             double acc = dot3(Fp, zc);
             BMPC_UNROLL
             for (int c = 0; c < 6; c++)
                 if (M < njc[c]) {
                     const double* pc = (c < 5) ? K.o[c + 2] : K.pl4;
                     double r[3] = {pc[0] - K.o[M][0], pc[1] - K.o[M][1], pc[2] - K.o[M][2]}, cc[3];
-                    cross3r(K.zx[M], r, cc);
-                    cross3r(K.zx[m], cc, zc);
+                    cross3r(zx[M], r, cc);
+                    cross3r(zx[m], cc, zc);
                     acc += dot3(Fc[c], zc);
                 }
             BMPC_UNROLL
             for (int j = 0; j < 7; j++) {
                 const int m1 = a < j ? a : j, M1 = a < j ? j : a;
-                double c1[3] = {Jl[0][M1], Jl[1][M1], Jl[2][M1]};
+                double c1[3] = {Jc[0][M1], Jc[1][M1], Jc[2][M1]};
                 double t1[3] = {0, 0, 0}, t2[3], dzm[3], dcM[3];
-                if (bq < m1) { cross3r(K.zx[bq], K.zx[m1], dzm); cross3r(dzm, c1, t1); }
+                if (bq < m1) { cross3r(zx[bq], zx[m1], dzm); cross3r(dzm, c1, t1); }
                 const int m2 = bq < M1 ? bq : M1, M2 = bq < M1 ? M1 : bq;
-                double c2[3] = {Jl[0][M2], Jl[1][M2], Jl[2][M2]};
-                cross3r(K.zx[m2], c2, dcM);
-                cross3r(K.zx[m1], dcM, t2);
+                double c2[3] = {Jc[0][M2], Jc[1][M2], Jc[2][M2]};
+                cross3r(zx[m2], c2, dcM);
+                cross3r(zx[m1], dcM, t2);
                 double lin = Fv[0] * (t1[0] + t2[0]) + Fv[1] * (t1[1] + t2[1]) + Fv[2] * (t1[2] + t2[2]);
                 double ang = 0;
                 if (a < j) {
                     double u1[3] = {0, 0, 0}, u2[3] = {0, 0, 0}, tmp[3];
-                    if (bq < a) { cross3r(K.zx[bq], K.zx[a], tmp); cross3r(tmp, K.zx[j], u1); }
-                    if (bq < j) { cross3r(K.zx[bq], K.zx[j], tmp); cross3r(K.zx[a], tmp, u2); }
+                    if (bq < a) { cross3r(zx[bq], zx[a], tmp); cross3r(tmp, zx[j], u1); }
+                    if (bq < j) { cross3r(zx[bq], zx[j], tmp); cross3r(zx[a], tmp, u2); }
                     ang = Fv[3] * (u1[0] + u2[0]) + Fv[4] * (u1[1] + u2[1]) + Fv[5] * (u1[2] + u2[2]);
                 }
                 acc += dq[j] * (lin + ang);
             }
             tri[sym7(a, bq)] = acc + (sc1 * sa[a] * sa[bq] + sbq[a] * sa[bq] + sa[a] * sbq[bq]);
+            BMPC_PIN(tri[sym7(a, bq)]);
         }
+    }
     BMPC_UNROLL
     for (int a = 0; a < 7; a++)
         BMPC_UNROLL
