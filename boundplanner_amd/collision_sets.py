@@ -80,12 +80,15 @@ def closest_pair_segment_polytope(A, b, p0, p1):
     return dist(phi)[1], phi
 
 
-def find_set_collision_avoidance(obs_sets, obs_points_sets, p0, p1, e_max=0.3):
-    """Greedy nearest-first separating halfspaces between segment [p0,p1] and the obstacles.
+def separating_halfspaces(obs_sets, obs_points_sets, p0, p1):
+    """Greedy nearest-first separating halfspaces between the segment [p0, p1] and the obstacles (ConvexSetFinder.py:330-375): the
+    nearest obstacle's halfspace through its closest point, shifted by 1 mm; obstacles whose vertices all lie behind it are
+    dropped; repeat.  A segment that touches its obstacle falls back to cp - p0, then to p1 - p0.  The one host statement of the
+    loop (the device's: csrc/bmpc_freespace.hpp); its callers prepend their own six rows.
 
     obs_sets: list of [A, b]; obs_points_sets: list of vertex arrays (n_v x 3).
-    Returns (A (n x 3), b (n), collision flag)."""
-    a_set, b_set = init_halfspaces_point(p0, e_max)
+    Returns (rows a (list of [3]), offsets b (list), collision flag)."""
+    a_set, b_set = [], []
     collision = False
     remain = list(range(len(obs_sets)))
     pts, closest, dists = {}, {}, {}
@@ -116,4 +119,12 @@ def find_set_collision_avoidance(obs_sets, obs_points_sets, p0, p1, e_max=0.3):
         remain = [i for i in remain if i not in drop]
         a_set.append(a)
         b_set.append(bh)
-    return np.array(a_set), np.array(b_set), collision
+    return a_set, b_set, collision
+
+
+def find_set_collision_avoidance(obs_sets, obs_points_sets, p0, p1, e_max=0.3):
+    """The per-step set of one collision point: the box of half-width e_max around p0, then the separating halfspaces of the
+    segment [p0, p1].  Returns (A (n x 3), b (n), collision flag)."""
+    a_set, b_set = init_halfspaces_point(p0, e_max)
+    a_sep, b_sep, collision = separating_halfspaces(obs_sets, obs_points_sets, p0, p1)
+    return np.array(a_set + a_sep), np.array(b_set + b_sep), collision

@@ -4,13 +4,13 @@ inscribed ellipsoid, and the segment-based set with its ellipsoid.
 Mirrors the planner-side interface of the reference's ConvexSetFinder
 (/root/reference/bound_planner/BoundPlanner/ConvexSetFinder.py): find_set_around_point (:190-240), compute_polyhedron
 (:423-469), compute_set_projs (:471-489), init_halfspaces (:377-398), find_set_collision_avoidance(..., compute_ellipsoid=True)
-(:309-375), mvie_socp / mvie_socp_fixed_mid (:512-560).  The per-step variant (limit_space=True) lives in collision_sets.py
-and on the device (csrc/bmpc_loop.hpp).  The third-party solvers of the reference are replaced by planner_opt.py.
+(:309-375), mvie_socp / mvie_socp_fixed_mid (:512-560).  The per-step variant (limit_space=True) lives in collision_sets.py, as
+does the greedy loop both variants share (separating_halfspaces; on the device csrc/bmpc_freespace.hpp).  The third-party solvers of the reference are replaced by planner_opt.py.
 """
 import numpy as np
 
 from . import planner_opt as PO
-from .collision_sets import closest_pair_segment_polytope
+from .collision_sets import separating_halfspaces
 
 
 def _inv_sym(q_inv):
@@ -110,31 +110,8 @@ class ConvexSetFinder:
         the obstacles (each shrunk by 1 mm).  Returns (A, b[, q_ellipse, centre], collision)."""
         p0, p1 = np.asarray(p0, float), np.asarray(p1, float)
         a_set, b_set = self.init_halfspaces()
-        collision = False
-        remain = list(range(len(self.obs_sets)))
-        pts, closest, dist = {}, {}, {}
-        for i in remain:
-            x, phi = closest_pair_segment_polytope(self.obs_sets[i][0], self.obs_sets[i][1] - 0.001, p0, p1)
-            pts[i], closest[i] = x, p0 + phi * (p1 - p0)
-            dist[i] = np.linalg.norm(x - closest[i])
-        while remain:
-            idx = min(remain, key=lambda i: dist[i])
-            cp = pts[idx]
-            a = cp - closest[idx]
-            na = np.linalg.norm(a)
-            if na < 1e-6:
-                collision = True
-                a = cp - p0
-                na = np.linalg.norm(a)
-                if na < 1e-6:
-                    a = p1 - p0
-                    na = np.linalg.norm(a)
-            a = a / na
-            bh = a @ cp - 0.001
-            drop = [idx] + [i for i in remain if i != idx and np.min(self.obs_points_sets[i] @ a - bh) >= -1e-4]
-            remain = [i for i in remain if i not in drop]
-            a_set.append(a); b_set.append(bh)
-        a_np, b_np = np.array(a_set), np.array(b_set)
+        a_sep, b_sep, collision = separating_halfspaces(self.obs_sets, self.obs_points_sets, p0, p1)
+        a_np, b_np = np.array(a_set + a_sep), np.array(b_set + b_sep)
         if compute_ellipsoid:
             q_inv, p_mid = self.mvie_socp(a_np, b_np)
             q_ellipse, _ = _inv_sym(q_inv)

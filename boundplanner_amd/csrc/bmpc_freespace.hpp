@@ -1,0 +1,254 @@
+// bmpc_freespace.hpp -- free space around a segment: the obstacle scene as the kernels see it, the closest pair between a segment
+// and an obstacle polytope, and the greedy nearest-first choice of separating halfspaces.  One statement of
+// ConvexSetFinder.find_set_collision_avoidance (ConvexSetFinder.py:309-375, with compute_set_projs_line :491-510) for both of its
+// users on the device: the per-step collision sets of the closed loop (bmpc_loop.hpp: loop_collision_pair, loop_prepare) and the
+// segment mode of the batched set kernel (bmpc_sets.hpp: sets_segment_lane).  The host states the same loop once, in
+// boundplanner_amd/collision_sets.py (separating_halfspaces).
+//
+// Written against the platform macros of bmpc_platform_hip.hpp, so that the CPU builds under tests/emu compile the identical source.
+#pragma once
+#include "bmpc_device.hpp"
+
+#ifndef BMPC_UNROLL
+#define BMPC_UNROLL _Pragma("unroll")
+#endif
+
+namespace bmpc {
+
+constexpr int LP_ROWS = 15;      // max_set_size: rows of an obstacle, and of a collision set of the loop
+
+// ---- the obstacle scene -----------------------------------------------------------------------------------
+// The obstacle polytopes {A x <= b} of a scene with their vertices.  The loop holds one scene for all rollouts
+// (bmpc_loop_set_obstacles) or a table with one per rollout (bmpc_loop_set_scenes), at most LP_MAXOBS obstacles each; the set kernel
+// wraps the same struct in its SetScene (bmpc_sets.hpp) with up to 32 obstacles.
+//
+// A A^T, which Hildreth's iteration reads, has two producers, on purpose.  The loop's is computed on the host by loop_pack_obstacles,
+// which also detects the boxes; the set kernel's comes from a small kernel (bmpc_sets_aat_kernel, sets_aat_row), because
+// bmpc_convex_sets_dev receives device pointers and no host code ever sees those rows.  The two are not bitwise interchangeable:
+// compiled for the CPU they differ in the sign of zero for axis-aligned rows (0 + (-0) against (-0) + (-0)), on the GPU by fused
+// rounding.  Each user is pinned to its own producer's bits; do not merge them.
+constexpr int LP_MAXOBS = 16;    // obstacle polytopes per scene
+constexpr int LP_NV = 32;        // vertices per obstacle
+constexpr int LP_CRES = 8;       // doubles per closest-pair result: x(3), y(3), distance, pad
+
+struct LoopScene {
+    int n_obs;
+    const double* A;      // [n_obs][15][3], rows beyond nrows are zero
+    const double* b;      // [n_obs][15]
+    const double* AAt;    // [n_obs][15][15]
+    const int* nrows;     // [n_obs]
+    const double* V;      // [n_obs][LP_NV][3]
+    const int* nv;        // [n_obs]
+    const double* box;    // [n_obs][6]: lo(3), hi(3) of obstacles that are axis-aligned boxes (is_box[o] != 0)
+    const int* is_box;    // [n_obs]
+};
+
+// host side (upload / CPU harness): is {A x <= b} (nr rows) an axis-aligned box?  If so lo/hi are its bounds.
+inline bool loop_detect_box(const double* A, const double* b, int nr, double* lo, double* hi) {
+    if (nr != 6) return false;
+    bool have[6] = {false, false, false, false, false, false};
+    for (int r = 0; r < 6; r++) {
+        int ax = -1;
+        for (int c = 0; c < 3; c++) {
+            const double a = A[3 * r + c];
+            if (a == 0.0) continue;
+            if ((a != 1.0 && a != -1.0) || ax >= 0) return false;
+            ax = c;
+        }
+        if (ax < 0) return false;
+        if (A[3 * r + ax] > 0) { if (have[ax]) return false; have[ax] = true; hi[ax] = b[r]; }
+        else { if (have[3 + ax]) return false; have[3 + ax] = true; lo[ax] = -b[r]; }
+    }
+    for (int i = 0; i < 6; i++) if (!have[i]) return false;
+    return true;
+}
+
+// host side: the device image of n obstacles given in the layout of bmpc_loop_set_obstacles (A [n][15][3], b [n][15], nrows, V [n][32][3],
+// nv) -- hd: A | b | AAt | V | box ([n][45], [n][15], [n][15][15], [n][32][3], [n][6]), hi: nrows | nv | is_box; rows and vertices beyond
+// nrows / nv are zero.  Both bmpc_loop_set_obstacles and bmpc_loop_set_scenes (all scenes' obstacles back to back) upload this image, so
+// that A A^T, which Hildreth's iteration reads, is rounded by the same host code whichever entry installed the obstacle.
+constexpr int LP_OBS_DOUBLES = 45 + LP_ROWS + LP_ROWS * LP_ROWS + 3 * LP_NV + 6, LP_OBS_INTS = 3;
+inline void loop_pack_obstacles(size_t n, const double* A, const double* b, const int* nrows, const double* V, const int* nv, double* hd, int* hi) {
+    const size_t nA = n * 45, nb = n * LP_ROWS, nAAt = n * LP_ROWS * LP_ROWS, nV = n * LP_NV * 3;
+    for (size_t i = 0; i < n * LP_OBS_DOUBLES; i++) hd[i] = 0.0;
+    for (size_t o = 0; o < n; o++) {
+        for (int r = 0; r < nrows[o]; r++) {
+            for (int c = 0; c < 3; c++) hd[45 * o + 3 * r + c] = A[45 * o + 3 * r + c];
+            hd[nA + LP_ROWS * o + r] = b[LP_ROWS * o + r];
+        }
+        for (int r = 0; r < nrows[o]; r++)
+            for (int q = 0; q < nrows[o]; q++) {
+                double sum = 0;
+                for (int c = 0; c < 3; c++) sum += A[45 * o + 3 * r + c] * A[45 * o + 3 * q + c];
+                hd[nA + nb + (size_t)LP_ROWS * LP_ROWS * o + LP_ROWS * r + q] = sum;
+            }
+        for (int v = 0; v < nv[o]; v++)
+            for (int c = 0; c < 3; c++) hd[nA + nb + nAAt + 3 * ((size_t)LP_NV * o + v) + c] = V[3 * (LP_NV * o + v) + c];
+        hi[o] = nrows[o]; hi[n + o] = nv[o];
+        double* bx = hd + nA + nb + nAAt + nV + 6 * o;
+        hi[2 * n + o] = loop_detect_box(A + 45 * o, b + LP_ROWS * o, nrows[o], bx, bx + 3) ? 1 : 0;
+    }
+}
+// the LoopScene over such an image at base addresses hd / hi (host or device)
+inline LoopScene loop_scene_over(size_t n, const double* hd, const int* hi) {
+    const size_t nA = n * 45, nb = n * LP_ROWS, nAAt = n * LP_ROWS * LP_ROWS, nV = n * LP_NV * 3;
+    return LoopScene{(int)n, hd, hd + nA, hd + nA + nb, hi, hd + nA + nb + nAAt, hi + n, hd + nA + nb + nAAt + nV, hi + 2 * n};
+}
+
+// ---- closest pair segment <-> polytope ----------------------------------------------------------------------
+// The algorithm of the host restatement (boundplanner_amd/collision_sets.py: golden section over the segment parameter, each
+// distance an exact projection by Hildreth's dual coordinate ascent), so that both sides agree to rounding.
+//
+// Euclidean projection of y onto {x: A x <= b - 0.001} (collision_sets._project_polytope).  Loops run over the fixed
+// LP_ROWS with an early exit at nr so that, unrolled, Ay / lam stay in registers (static indices)
+BMPC_INL void lp_project_polytope(const double* A, const double* b, const double* AAt, int nr, const double* y, double* x) {
+    double Ay[LP_ROWS], lam[LP_ROWS];
+    bool inside = true;
+    BMPC_UNROLL
+    for (int i = 0; i < LP_ROWS; i++) {
+        Ay[i] = 0.0; lam[i] = 0.0;
+        if (i < nr) {
+            Ay[i] = A[3 * i] * y[0] + A[3 * i + 1] * y[1] + A[3 * i + 2] * y[2];
+            if (Ay[i] - (b[i] - 0.001) > 1e-12) inside = false;
+        }
+    }
+    x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
+    if (inside) return;
+    for (int sweep = 0; sweep < 1200; sweep++) {
+        double max_change = 0.0;
+        BMPC_UNROLL
+        for (int i = 0; i < LP_ROWS; i++) {
+            if (i < nr) {
+                double r = Ay[i];
+                BMPC_UNROLL
+                for (int j = 0; j < LP_ROWS; j++)
+                    if (j < nr) r -= AAt[LP_ROWS * i + j] * lam[j];
+                r -= (b[i] - 0.001);
+                const double dg = fmax(AAt[LP_ROWS * i + i], 1e-16);
+                const double nw = fmax(0.0, lam[i] + r / dg);
+                max_change = fmax(max_change, fabs(nw - lam[i]));
+                lam[i] = nw;
+            }
+        }
+        if (max_change < 1e-13) break;
+    }
+    BMPC_UNROLL
+    for (int i = 0; i < LP_ROWS; i++)
+        if (i < nr)
+            for (int c = 0; c < 3; c++) x[c] -= A[3 * i + c] * lam[i];
+}
+
+// distance from the segment point p0 + phi d to the polytope {A x <= b - 0.001}; box != null: the polytope is the
+// axis-aligned box [lo, hi] and its exact projection is a clamp (what Hildreth's iteration converges to)
+BMPC_INL double lp_seg_dist(const double* A, const double* b, const double* AAt, int nr, const double* box, const double* p0,
+                            const double* d, double phi, double* x) {
+    const double y[3] = {p0[0] + phi * d[0], p0[1] + phi * d[1], p0[2] + phi * d[2]};
+    if (box) {
+        for (int c = 0; c < 3; c++) x[c] = fmin(fmax(y[c], box[c] + 0.001), box[3 + c] - 0.001);
+    } else {
+        lp_project_polytope(A, b, AAt, nr, y, x);
+    }
+    return sqrt((y[0] - x[0]) * (y[0] - x[0]) + (y[1] - x[1]) * (y[1] - x[1]) + (y[2] - x[2]) * (y[2] - x[2]));
+}
+
+// closest pair segment <-> polytope (collision_sets.closest_pair_segment_polytope); out: x, y = p0 + phi d, distance
+BMPC_DEV void loop_closest_pair(const double* A, const double* b, const double* AAt, int nr, const double* box, const double* p0,
+                                const double* p1, double* out) {
+    const double d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+    double x[3], phi = 0.0;
+    if (sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) >= 1e-12) {
+        double lo = 0.0, hi = 1.0;
+        const double gr = (sqrt(5.0) - 1.0) / 2.0;
+        double c = hi - gr * (hi - lo), e = lo + gr * (hi - lo);
+        double fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x), fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x);
+        for (int it = 0; it < 80; it++) {
+            if (fc < fe) {
+                hi = e; e = c; fe = fc;
+                c = hi - gr * (hi - lo);
+                fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x);
+            } else {
+                lo = c; c = e; fc = fe;
+                e = lo + gr * (hi - lo);
+                fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x);
+            }
+        }
+        const double pm = 0.5 * (lo + hi);
+        const double f0 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 0.0, x), f1 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 1.0, x),
+                     fm = lp_seg_dist(A, b, AAt, nr, box, p0, d, pm, x);
+        // min over (distance, phi) pairs in the order (0, 1, pm): ties go to the smaller phi
+        double best = f0; phi = 0.0;
+        if (f1 < best) { best = f1; phi = 1.0; }
+        if (fm < best || (fm == best && pm < phi)) { best = fm; phi = pm; }
+    }
+    const double dist = lp_seg_dist(A, b, AAt, nr, box, p0, d, phi, x);
+    for (int c = 0; c < 3; c++) { out[c] = x[c]; out[3 + c] = p0[c] + phi * d[c]; }
+    out[6] = dist; out[7] = phi;
+}
+
+// ---- greedy nearest-first separating halfspaces (ConvexSetFinder.py:330-375) ----------------------------
+// obstacles still to be separated after the halfspace (a, bh): those with a vertex in front of it (min_v a.v - bh < -1e-4)
+BMPC_INL unsigned sp_drop_behind(const LoopScene& sc, unsigned remain, const double* a, double bh) {
+    for (int i = 0; i < sc.n_obs; i++) {
+        if (!((remain >> i) & 1u)) continue;
+        double mn = __builtin_inf();
+        const int nv = sc.nv[i];
+        for (int v = 0; v < nv; v++) {
+            const double* vv = sc.V + 3 * (LP_NV * i + v);
+            mn = fmin(mn, vv[0] * a[0] + vv[1] * a[1] + vv[2] * a[2] - bh);
+        }
+        if (mn >= -1e-4) remain &= ~(1u << i);
+    }
+    return remain;
+}
+
+// nearest remaining obstacle (first index on ties, as Python's min)
+BMPC_INL int sp_nearest(int n_obs, unsigned remain, const double* dist, int ds) {
+    int idx = -1;
+    double bd = 0.0;
+    for (int i = 0; i < n_obs; i++) {
+        if (!((remain >> i) & 1u)) continue;
+        const double d = dist[i * ds];
+        if (idx < 0 || d < bd) { idx = i; bd = d; }
+    }
+    return idx;
+}
+
+// The halfspaces that separate the segment [p0, p1] from the obstacles of sc (at most 32: `remain` is a bit mask), nearest obstacle
+// first, each shifted by 1 mm; an obstacle that lies behind a chosen halfspace needs none of its own.  pair(i): the closest-pair
+// record of obstacle i (loop_closest_pair: point of the obstacle, point of the segment, distance) -- the loop hands back what its
+// closest-pair pass stored, the set kernel computes it again; dist[i * ds]: the distances of those records.  The rows are appended to
+// the n rows already in A [cap][3], b [cap].  Returns the new row count, or FS_OVERFLOW when a row does not fit (the host raises
+// there; rows up to cap are written); touched: the segment touches an obstacle, whose row then points along cp - p0 or p1 - p0.
+constexpr int FS_OVERFLOW = -1;
+template <class Pair>
+BMPC_INL int separating_halfspaces(const LoopScene& sc, Pair pair, const double* dist, int ds, const double* p0, const double* p1,
+                                   int cap, double* A, double* b, int n, bool& touched) {
+    touched = false;
+    unsigned remain = 0;
+    for (int i = 0; i < sc.n_obs; i++) remain |= 1u << i;
+    while (remain) {
+        const int idx = sp_nearest(sc.n_obs, remain, dist, ds);
+        const double* cp = pair(idx);
+        double a[3] = {cp[0] - cp[3], cp[1] - cp[4], cp[2] - cp[5]};
+        double na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        if (na < 1e-6) {          // the segment touches the obstacle
+            touched = true;
+            for (int k = 0; k < 3; k++) a[k] = cp[k] - p0[k];
+            na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+            if (na < 1e-6) {
+                for (int k = 0; k < 3; k++) a[k] = p1[k] - p0[k];
+                na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+            }
+        }
+        for (int k = 0; k < 3; k++) a[k] /= na;
+        const double bh = a[0] * cp[0] + a[1] * cp[1] + a[2] * cp[2] - 0.001;
+        remain = sp_drop_behind(sc, remain & ~(1u << idx), a, bh);
+        if (n >= cap) return FS_OVERFLOW;
+        for (int k = 0; k < 3; k++) A[3 * n + k] = a[k];
+        b[n] = bh;
+        n++;
+    }
+    return n;
+}
+
+}  // namespace bmpc

@@ -18,22 +18,19 @@
 // vector below: built on the host (boundplanner_amd/reference_path.py, bound_mpc.py) and serialised by
 // boundplanner_amd/device_loop.py pack_state, or written on the device by loop_install_path, which restates
 // exactly that host code.  Scenes with obstacles are handled on the device as well: the per-step collision
-// sets come from the closest-pair pass further down (one shared scene, or one scene per rollout).
+// sets come from a closest-pair pass, one thread per (rollout, collision point, obstacle) (loop_collision_pair), and the greedy
+// choice of separating halfspaces per (rollout, collision point) inside loop_prepare -- the scene image, the closest pair and the
+// greedy routine are those of bmpc_freespace.hpp, shared with the set kernel (one shared scene, or one scene per rollout).
 //
 // Written against the platform macros of bmpc_platform_hip.hpp so that tests/emu/emu_loop.cpp can run
 // the identical source on the CPU against the reference's closed-loop trace (test infrastructure only).
 #pragma once
-#include "bmpc_device.hpp"
-
-#ifndef BMPC_UNROLL
-#define BMPC_UNROLL _Pragma("unroll")
-#endif
+#include "bmpc_freespace.hpp"
 
 namespace bmpc {
 
 constexpr int LP_NL = 11;        // via points + nr_segs-1 padded copies, at most (8 via points)
 constexpr int LP_S = 4;          // nr_segs
-constexpr int LP_ROWS = 15;      // max_set_size
 constexpr int LP_NMAX = 64;      // horizon bound of the solver
 constexpr int LP_LOGW = 24;      // doubles per (step, rollout) log row
 // Optional per-(step, selected rollout) record with the content of the reference's trace message (boundmpcmsg/msg/MPCData.msg:1-64):
@@ -247,81 +244,6 @@ BMPC_INL void lp_path_update(double* S, bool sw) {
     lp_set_point(S, LP_S - 1);
 }
 
-// ---- per-step collision sets with obstacles (ConvexSetFinder.find_set_collision_avoidance, ---------
-// ConvexSetFinder.py:309-375, with compute_set_projs_line :491-510): the obstacle polytopes of a scene, one scene for all
-// rollouts (bmpc_loop_set_obstacles) or one per rollout out of a table (bmpc_loop_set_scenes).  The closest pair between the segment [p(q0), p(qf)] of a collision point and a polytope is the
-// algorithm of the host restatement (boundplanner_amd/collision_sets.py: golden section over the segment
-// parameter, each distance an exact projection by Hildreth's dual coordinate ascent), so that both sides agree
-// to rounding; one thread per (rollout, collision point, obstacle), then the greedy nearest-first selection of
-// separating halfspaces per (rollout, collision point) inside loop_prepare.
-constexpr int LP_MAXOBS = 16;    // obstacle polytopes per scene
-constexpr int LP_NV = 32;        // vertices per obstacle
-constexpr int LP_CRES = 8;       // doubles per closest-pair result: x(3), y(3), distance, pad
-
-struct LoopScene {
-    int n_obs;
-    const double* A;      // [n_obs][15][3], rows beyond nrows are zero
-    const double* b;      // [n_obs][15]
-    const double* AAt;    // [n_obs][15][15]
-    const int* nrows;     // [n_obs]
-    const double* V;      // [n_obs][LP_NV][3]
-    const int* nv;        // [n_obs]
-    const double* box;    // [n_obs][6]: lo(3), hi(3) of obstacles that are axis-aligned boxes (is_box[o] != 0)
-    const int* is_box;    // [n_obs]
-};
-
-// host side (upload / CPU harness): is {A x <= b} (nr rows) an axis-aligned box?  If so lo/hi are its bounds.
-inline bool loop_detect_box(const double* A, const double* b, int nr, double* lo, double* hi) {
-    if (nr != 6) return false;
-    bool have[6] = {false, false, false, false, false, false};
-    for (int r = 0; r < 6; r++) {
-        int ax = -1;
-        for (int c = 0; c < 3; c++) {
-            const double a = A[3 * r + c];
-            if (a == 0.0) continue;
-            if ((a != 1.0 && a != -1.0) || ax >= 0) return false;
-            ax = c;
-        }
-        if (ax < 0) return false;
-        if (A[3 * r + ax] > 0) { if (have[ax]) return false; have[ax] = true; hi[ax] = b[r]; }
-        else { if (have[3 + ax]) return false; have[3 + ax] = true; lo[ax] = -b[r]; }
-    }
-    for (int i = 0; i < 6; i++) if (!have[i]) return false;
-    return true;
-}
-
-// host side: the device image of n obstacles given in the layout of bmpc_loop_set_obstacles (A [n][15][3], b [n][15], nrows, V [n][32][3],
-// nv) -- hd: A | b | AAt | V | box ([n][45], [n][15], [n][15][15], [n][32][3], [n][6]), hi: nrows | nv | is_box; rows and vertices beyond
-// nrows / nv are zero.  Both bmpc_loop_set_obstacles and bmpc_loop_set_scenes (all scenes' obstacles back to back) upload this image, so
-// that A A^T, which Hildreth's iteration reads, is rounded by the same host code whichever entry installed the obstacle.
-constexpr int LP_OBS_DOUBLES = 45 + LP_ROWS + LP_ROWS * LP_ROWS + 3 * LP_NV + 6, LP_OBS_INTS = 3;
-inline void loop_pack_obstacles(size_t n, const double* A, const double* b, const int* nrows, const double* V, const int* nv, double* hd, int* hi) {
-    const size_t nA = n * 45, nb = n * LP_ROWS, nAAt = n * LP_ROWS * LP_ROWS, nV = n * LP_NV * 3;
-    for (size_t i = 0; i < n * LP_OBS_DOUBLES; i++) hd[i] = 0.0;
-    for (size_t o = 0; o < n; o++) {
-        for (int r = 0; r < nrows[o]; r++) {
-            for (int c = 0; c < 3; c++) hd[45 * o + 3 * r + c] = A[45 * o + 3 * r + c];
-            hd[nA + LP_ROWS * o + r] = b[LP_ROWS * o + r];
-        }
-        for (int r = 0; r < nrows[o]; r++)
-            for (int q = 0; q < nrows[o]; q++) {
-                double sum = 0;
-                for (int c = 0; c < 3; c++) sum += A[45 * o + 3 * r + c] * A[45 * o + 3 * q + c];
-                hd[nA + nb + (size_t)LP_ROWS * LP_ROWS * o + LP_ROWS * r + q] = sum;
-            }
-        for (int v = 0; v < nv[o]; v++)
-            for (int c = 0; c < 3; c++) hd[nA + nb + nAAt + 3 * ((size_t)LP_NV * o + v) + c] = V[3 * (LP_NV * o + v) + c];
-        hi[o] = nrows[o]; hi[n + o] = nv[o];
-        double* bx = hd + nA + nb + nAAt + nV + 6 * o;
-        hi[2 * n + o] = loop_detect_box(A + 45 * o, b + LP_ROWS * o, nrows[o], bx, bx + 3) ? 1 : 0;
-    }
-}
-// the LoopScene over such an image at base addresses hd / hi (host or device)
-inline LoopScene loop_scene_over(size_t n, const double* hd, const int* hi) {
-    const size_t nA = n * 45, nb = n * LP_ROWS, nAAt = n * LP_ROWS * LP_ROWS, nV = n * LP_NV * 3;
-    return LoopScene{(int)n, hd, hd + nA, hd + nA + nb, hi, hd + nA + nb + nAAt, hi + n, hd + nA + nb + nAAt + nV, hi + 2 * n};
-}
-
 // ---- one scene per rollout (bmpc_loop_set_scenes) ----------------------------------------------------
 // The obstacles of all scenes lie back to back in `all` (only the obstacles that exist); scene s owns obstacles first[s] ..
 // first[s + 1] - 1.  Which scene a rollout looks at is configuration of the loop, not rollout state: scene[r], -1 = no obstacles.
@@ -344,92 +266,6 @@ BMPC_INL LoopScene loop_scene_of(const LoopSceneTable& t, int r) {
 // ([point][obstacle of the rollout's own scene], the layout loop_prepare reads)
 BMPC_INL size_t loop_colres_of(const LoopSceneTable& t, int r) { return (size_t)r * 6 * t.max_obs * LP_CRES; }
 
-// Euclidean projection of y onto {x: A x <= b - 0.001} (collision_sets._project_polytope).  Loops run over the fixed
-// LP_ROWS with an early exit at nr so that, unrolled, Ay / lam stay in registers (static indices)
-BMPC_INL void lp_project_polytope(const double* A, const double* b, const double* AAt, int nr, const double* y, double* x) {
-    double Ay[LP_ROWS], lam[LP_ROWS];
-    bool inside = true;
-    BMPC_UNROLL
-    for (int i = 0; i < LP_ROWS; i++) {
-        Ay[i] = 0.0; lam[i] = 0.0;
-        if (i < nr) {
-            Ay[i] = A[3 * i] * y[0] + A[3 * i + 1] * y[1] + A[3 * i + 2] * y[2];
-            if (Ay[i] - (b[i] - 0.001) > 1e-12) inside = false;
-        }
-    }
-    x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
-    if (inside) return;
-    for (int sweep = 0; sweep < 1200; sweep++) {
-        double max_change = 0.0;
-        BMPC_UNROLL
-        for (int i = 0; i < LP_ROWS; i++) {
-            if (i < nr) {
-                double r = Ay[i];
-                BMPC_UNROLL
-                for (int j = 0; j < LP_ROWS; j++)
-                    if (j < nr) r -= AAt[LP_ROWS * i + j] * lam[j];
-                r -= (b[i] - 0.001);
-                const double dg = fmax(AAt[LP_ROWS * i + i], 1e-16);
-                const double nw = fmax(0.0, lam[i] + r / dg);
-                max_change = fmax(max_change, fabs(nw - lam[i]));
-                lam[i] = nw;
-            }
-        }
-        if (max_change < 1e-13) break;
-    }
-    BMPC_UNROLL
-    for (int i = 0; i < LP_ROWS; i++)
-        if (i < nr)
-            for (int c = 0; c < 3; c++) x[c] -= A[3 * i + c] * lam[i];
-}
-
-// distance from the segment point p0 + phi d to the polytope {A x <= b - 0.001}; box != null: the polytope is the
-// axis-aligned box [lo, hi] and its exact projection is a clamp (what Hildreth's iteration converges to)
-BMPC_INL double lp_seg_dist(const double* A, const double* b, const double* AAt, int nr, const double* box, const double* p0,
-                            const double* d, double phi, double* x) {
-    const double y[3] = {p0[0] + phi * d[0], p0[1] + phi * d[1], p0[2] + phi * d[2]};
-    if (box) {
-        for (int c = 0; c < 3; c++) x[c] = fmin(fmax(y[c], box[c] + 0.001), box[3 + c] - 0.001);
-    } else {
-        lp_project_polytope(A, b, AAt, nr, y, x);
-    }
-    return sqrt((y[0] - x[0]) * (y[0] - x[0]) + (y[1] - x[1]) * (y[1] - x[1]) + (y[2] - x[2]) * (y[2] - x[2]));
-}
-
-// closest pair segment <-> polytope (collision_sets.closest_pair_segment_polytope); out: x, y = p0 + phi d, distance
-BMPC_DEV void loop_closest_pair(const double* A, const double* b, const double* AAt, int nr, const double* box, const double* p0,
-                                const double* p1, double* out) {
-    const double d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    double x[3], phi = 0.0;
-    if (sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) >= 1e-12) {
-        double lo = 0.0, hi = 1.0;
-        const double gr = (sqrt(5.0) - 1.0) / 2.0;
-        double c = hi - gr * (hi - lo), e = lo + gr * (hi - lo);
-        double fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x), fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x);
-        for (int it = 0; it < 80; it++) {
-            if (fc < fe) {
-                hi = e; e = c; fe = fc;
-                c = hi - gr * (hi - lo);
-                fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x);
-            } else {
-                lo = c; c = e; fc = fe;
-                e = lo + gr * (hi - lo);
-                fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x);
-            }
-        }
-        const double pm = 0.5 * (lo + hi);
-        const double f0 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 0.0, x), f1 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 1.0, x),
-                     fm = lp_seg_dist(A, b, AAt, nr, box, p0, d, pm, x);
-        // min over (distance, phi) pairs in the order (0, 1, pm): ties go to the smaller phi
-        double best = f0; phi = 0.0;
-        if (f1 < best) { best = f1; phi = 1.0; }
-        if (fm < best || (fm == best && pm < phi)) { best = fm; phi = pm; }
-    }
-    const double dist = lp_seg_dist(A, b, AAt, nr, box, p0, d, phi, x);
-    for (int c = 0; c < 3; c++) { out[c] = x[c]; out[3 + c] = p0[c] + phi * d[c]; }
-    out[6] = dist; out[7] = phi;
-}
-
 // one (rollout, collision point, obstacle) of the closest-pair pass
 BMPC_DEV void loop_collision_pair(const RobotConst* rc, const LoopScene& sc, const double* S, int pt, int ob, double* out) {
     Kin k0, kf;
@@ -437,48 +273,6 @@ BMPC_DEV void loop_collision_pair(const RobotConst* rc, const LoopScene& sc, con
     kin_eval(rc, S + LS_qf, kf);
     loop_closest_pair(sc.A + 45 * ob, sc.b + LP_ROWS * ob, sc.AAt + LP_ROWS * LP_ROWS * ob, sc.nrows[ob],
                       sc.is_box[ob] ? sc.box + 6 * ob : nullptr, k0.pc[pt], kf.pc[pt], out);
-}
-
-// greedy nearest-first separating halfspaces of one collision point (ConvexSetFinder.py:330-375); res: the
-// closest-pair results of this (rollout, point) for all obstacles; rows 6.. of a[15][3], b[15] are appended.
-// Returns the number of rows, or -1 when they do not fit max_set_size (the host raises there).
-BMPC_INL int lp_collision_rows(const LoopScene& sc, const double* res, const double* p0, const double* p1, double a[][3], double* b) {
-    int n = 6;
-    bool remain[LP_MAXOBS];
-    for (int i = 0; i < sc.n_obs; i++) remain[i] = true;
-    for (;;) {
-        int idx = -1;
-        for (int i = 0; i < sc.n_obs; i++)
-            if (remain[i] && (idx < 0 || res[LP_CRES * i + 6] < res[LP_CRES * idx + 6])) idx = i;
-        if (idx < 0) break;
-        const double* cp = res + LP_CRES * idx;
-        double av[3] = {cp[0] - cp[3], cp[1] - cp[4], cp[2] - cp[5]};
-        double na = sqrt(av[0] * av[0] + av[1] * av[1] + av[2] * av[2]);
-        if (na < 1e-6) {          // the segment touches the obstacle
-            for (int c = 0; c < 3; c++) av[c] = cp[c] - p0[c];
-            na = sqrt(av[0] * av[0] + av[1] * av[1] + av[2] * av[2]);
-            if (na < 1e-6) {
-                for (int c = 0; c < 3; c++) av[c] = p1[c] - p0[c];
-                na = sqrt(av[0] * av[0] + av[1] * av[1] + av[2] * av[2]);
-            }
-        }
-        for (int c = 0; c < 3; c++) av[c] /= na;
-        const double bh = av[0] * cp[0] + av[1] * cp[1] + av[2] * cp[2] - 0.001;
-        remain[idx] = false;
-        for (int i = 0; i < sc.n_obs; i++) {
-            if (!remain[i]) continue;
-            double mn = 1e300;
-            for (int v = 0; v < sc.nv[i]; v++) {
-                const double* vv = sc.V + 3 * (LP_NV * i + v);
-                mn = fmin(mn, vv[0] * av[0] + vv[1] * av[1] + vv[2] * av[2] - bh);
-            }
-            if (mn >= -1e-4) remain[i] = false;     // entirely behind the new halfspace
-        }
-        if (n >= LP_ROWS) return -1;
-        a[n][0] = av[0]; a[n][1] = av[1]; a[n][2] = av[2]; b[n] = bh;
-        n++;
-    }
-    return n;
 }
 
 // ---- before the solve: BoundMPC.step up to the solver call ---------------------------------------
@@ -601,8 +395,11 @@ BMPC_DEV void loop_prepare(const RobotConst* rc, int N, double* S, const double*
         }
         int n = 6;
         if (obst) {
-            n = lp_collision_rows(*sc, colres + LP_CRES * sc->n_obs * j, k.pc[j], kf.pc[j], a, b);
-            if (n < 0) { S[LS_dead] = 2.0; n = LP_ROWS; }       // more rows than max_set_size: the host raises
+            const double* res = colres + LP_CRES * sc->n_obs * j;      // the closest pairs of this point, [obstacle][LP_CRES]
+            bool touched;
+            n = separating_halfspaces(*sc, [res](int i) { return res + LP_CRES * i; }, res + 6, LP_CRES, k.pc[j], kf.pc[j], LP_ROWS,
+                                      &a[0][0], b, n, touched);
+            if (n == FS_OVERFLOW) { S[LS_dead] = 2.0; n = LP_ROWS; }       // more rows than max_set_size: the host raises
         }
         for (int c = 0; c < 3; c++)
             for (int r = 0; r < LP_ROWS; r++) p[P_ASETJ + 45 * j + LP_ROWS * c + r] = (r < n) ? a[r][c] : 0.0;

@@ -12,7 +12,8 @@ using namespace bmpc;
 
 constexpr int SETS_NT = 64;   // one wavefront per workgroup: 64 x 32 doubles of LDS (16 KiB)
 
-// A A^T of every obstacle (the segment mode's projections): one thread per (obstacle, row i)
+// A A^T of every obstacle (the segment mode's projections): one thread per (obstacle, row i).  On the device because bmpc_convex_sets_dev
+// hands in device pointers; why this is not the loop's host-side A A^T: bmpc_freespace.hpp
 __global__ void bmpc_sets_aat_kernel(int n_obs, const double* A, const int* nrows, double* AAt) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_obs * SETS_OROWS) return;
@@ -56,10 +57,10 @@ extern "C" hipError_t bmpc_launch_sets(int B, int segment, int fixed_mid, int op
                                        const double* p0, const double* p1, double* A, double* b, int* nrows, double* q, double* c,
                                        int* rounds, int* newton, int* collision, int* status, hipStream_t st) {
     SetScene s = *sc;
-    if (segment && s.n_obs > 0) {
-        const int n = s.n_obs * SETS_OROWS;
-        hipLaunchKernelGGL(bmpc_sets_aat_kernel, dim3((n + 63) / 64), dim3(64), 0, st, s.n_obs, s.A, s.nrows, AAt_ws);
-        s.AAt = AAt_ws;
+    if (segment && s.obs.n_obs > 0) {
+        const int n = s.obs.n_obs * SETS_OROWS;
+        hipLaunchKernelGGL(bmpc_sets_aat_kernel, dim3((n + 63) / 64), dim3(64), 0, st, s.obs.n_obs, s.obs.A, s.obs.nrows, AAt_ws);
+        s.obs.AAt = AAt_ws;
     }
     hipLaunchKernelGGL(bmpc_sets_kernel, dim3((unsigned)((B + SETS_NT - 1) / SETS_NT)), dim3(SETS_NT), 0, st, B, segment, fixed_mid,
                        optimize, s, p0, p1, A, b, nrows, q, c, rounds, newton, collision, status);

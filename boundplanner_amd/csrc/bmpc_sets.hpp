@@ -5,14 +5,15 @@
 //   find_set_around_point        alternate polyhedron growth and a maximum-volume inscribed ellipsoid (MVIE), at most SETS_MAX_ROUNDS
 //   compute_polyhedron / _projs  nearest obstacle first, distances in the metric of the current ellipsoid, obstacles behind a chosen
 //                                halfspace dropped
-//   find_set_collision_avoidance the segment variant (closest pairs by loop_closest_pair of bmpc_loop.hpp), with its free-centre MVIE
+//   find_set_collision_avoidance the segment variant (closest pairs and the greedy halfspaces: bmpc_freespace.hpp, shared with the
+//                                device loop), with its free-centre MVIE
 //   planner_opt.mvie             log-barrier Newton method in the parameterisation of the reference's SOCP
 //
 // Storage: the obstacle rows and vertices are read from global memory (the same for every lane: cached); the
 // rows of the set being grown live in the lane's output rows A [SETS_ROWS][3], b [SETS_ROWS]; the per-obstacle distances of a round
 // live in `dist` with stride `ds` (LDS in the kernel).  No array here is indexed by a runtime value, so nothing goes to scratch.
 #pragma once
-#include "bmpc_loop.hpp"
+#include "bmpc_freespace.hpp"
 
 namespace bmpc {
 
@@ -26,14 +27,12 @@ constexpr int SETS_MAX_ROUNDS = 5;   // ConvexSetFinder.max_iter
 constexpr int SETS_OK = 0, SETS_VIOLATES = 1, SETS_TOO_MANY_ROWS = 2, SETS_NO_INTERIOR = 3, SETS_NUMERICAL = 4;
 
 struct SetScene {
-    int n_obs;
-    const double* A;      // [n_obs][15][3], rows beyond nrows ignored
-    const double* b;      // [n_obs][15]
-    const int* nrows;     // [n_obs]
-    const double* V;      // [n_obs][32][3]
-    const int* nv;        // [n_obs]
-    const double* AAt;    // [n_obs][15][15] (A A^T of the obstacle: the segment mode's closest pairs)
+    LoopScene obs;        // the obstacles; AAt is set in segment mode only (its closest pairs), box / is_box never: no box shortcut here
     double e_min[3], e_max[3];
+    // in the argument order of bmpc_convex_sets
+    SetScene(int n_obs, const double* A, const double* b, const int* nrows, const double* V, const int* nv, const double* AAt,
+             const double (&lo)[3], const double (&hi)[3])
+        : obs{n_obs, A, b, AAt, nrows, V, nv, nullptr, nullptr}, e_min{lo[0], lo[1], lo[2]}, e_max{hi[0], hi[1], hi[2]} {}
 };
 
 BMPC_INL constexpr int sp_tri(int i, int j) { return i * (i + 1) / 2 + j; }   // packed lower triangle, j <= i
@@ -112,13 +111,13 @@ BMPC_INL bool sp_newton_dir(const double* H, const double* g, double* dx) {
 // Row r of obstacle o in the coordinates u of x = p0 + E u (E symmetric), scaled to unit length: a' = E a / |E a|,
 // b' = (b - a.p0) / |E a|.  False for a zero row (project_polytope drops it).
 BMPC_INL bool sp_urow(const SetScene& sc, int o, int r, const double* E, const double* p0, double* ap, double& bp) {
-    const double* a = sc.A + 3 * (SETS_OROWS * o + r);
+    const double* a = sc.obs.A + 3 * (SETS_OROWS * o + r);
     const double a0 = a[0], a1 = a[1], a2 = a[2];
     // a^T E (E symmetric: the row of A @ E)
     ap[0] = a0 * E[0] + a1 * E[3] + a2 * E[6];
     ap[1] = a0 * E[1] + a1 * E[4] + a2 * E[7];
     ap[2] = a0 * E[2] + a1 * E[5] + a2 * E[8];
-    bp = sc.b[SETS_OROWS * o + r] - (a0 * p0[0] + a1 * p0[1] + a2 * p0[2]);
+    bp = sc.obs.b[SETS_OROWS * o + r] - (a0 * p0[0] + a1 * p0[1] + a2 * p0[2]);
     const double n = sqrt(ap[0] * ap[0] + ap[1] * ap[1] + ap[2] * ap[2]);
     if (!(n > 0.0)) return false;
     ap[0] /= n; ap[1] /= n; ap[2] /= n; bp /= n;
@@ -127,7 +126,7 @@ BMPC_INL bool sp_urow(const SetScene& sc, int o, int r, const double* E, const d
 
 // is u feasible for every (non-zero) row of obstacle o: a'.u - b' <= tol
 BMPC_INL bool sp_ufeas(const SetScene& sc, int o, const double* E, const double* p0, const double* u, double tol) {
-    const int nr = sc.nrows[o];
+    const int nr = sc.obs.nrows[o];
     for (int r = 0; r < nr; r++) {
         double ap[3], bp;
         if (!sp_urow(sc, o, r, E, p0, ap, bp)) continue;
@@ -142,7 +141,7 @@ BMPC_INL bool sp_ufeas(const SetScene& sc, int o, const double* E, const double*
 // |u| reaches 1e4, where an absolute 1e-10 is below the rounding of a'.u.
 // Returns the point p0 + E u in world coordinates; false when no KKT point exists (an empty obstacle).
 BMPC_INL bool sp_project(const SetScene& sc, int o, const double* E, const double* p0, double* pt) {
-    const int nr = sc.nrows[o];
+    const int nr = sc.obs.nrows[o];
     double u[3] = {0.0, 0.0, 0.0};
     bool inside = true;
     for (int r = 0; r < nr && inside; r++) {
@@ -238,38 +237,11 @@ BMPC_INL void sp_init_rows(const SetScene& sc, double* A, double* b) {      // i
     }
 }
 
-// obstacles still to be separated after the halfspace (a, bh): those with a vertex in front of it (min_v a.v - bh < -1e-4)
-BMPC_INL unsigned sp_drop_behind(const SetScene& sc, unsigned remain, const double* a, double bh) {
-    for (int i = 0; i < sc.n_obs; i++) {
-        if (!((remain >> i) & 1u)) continue;
-        double mn = __builtin_inf();
-        const int nv = sc.nv[i];
-        for (int v = 0; v < nv; v++) {
-            const double* vv = sc.V + 3 * (SETS_NV * i + v);
-            mn = fmin(mn, vv[0] * a[0] + vv[1] * a[1] + vv[2] * a[2] - bh);
-        }
-        if (mn >= -1e-4) remain &= ~(1u << i);
-    }
-    return remain;
-}
-
-// nearest remaining obstacle (first index on ties, as Python's min)
-BMPC_INL int sp_nearest(int n_obs, unsigned remain, const double* dist, int ds) {
-    int idx = -1;
-    double bd = 0.0;
-    for (int i = 0; i < n_obs; i++) {
-        if (!((remain >> i) & 1u)) continue;
-        const double d = dist[i * ds];
-        if (idx < 0 || d < bd) { idx = i; bd = d; }
-    }
-    return idx;
-}
-
 // compute_polyhedron: the rows of one round around p (E = q_inv, Qe = q_ellipse); returns the row count or a negative status
 BMPC_INL int sp_polyhedron(const SetScene& sc, const double* E, const double* Qe, const double* p, double* dist, int ds, double* A, double* b) {
     sp_init_rows(sc, A, b);
     unsigned remain = 0;
-    for (int i = 0; i < sc.n_obs; i++) {
+    for (int i = 0; i < sc.obs.n_obs; i++) {
         double pt[3];
         if (!sp_project(sc, i, E, p, pt)) return -SETS_NUMERICAL;
         const double d[3] = {pt[0] - p[0], pt[1] - p[1], pt[2] - p[2]};
@@ -287,7 +259,7 @@ BMPC_INL int sp_polyhedron(const SetScene& sc, const double* E, const double* Qe
         for (int c = 0; c < 3; c++) Q2[3 * r + c] = Qe[3 * r] * Qe[3 * c] + Qe[3 * r + 1] * Qe[3 * c + 1] + Qe[3 * r + 2] * Qe[3 * c + 2];
     int n = 6;
     while (remain) {
-        const int idx = sp_nearest(sc.n_obs, remain, dist, ds);
+        const int idx = sp_nearest(sc.obs.n_obs, remain, dist, ds);
         if (dist[idx * ds] < 0.99) return -SETS_VIOLATES;        // the host raises "Ellipse violates constraints"
         double cp[3];
         sp_project(sc, idx, E, p, cp);                            // the same projection again (deterministic)
@@ -298,7 +270,7 @@ BMPC_INL int sp_polyhedron(const SetScene& sc, const double* E, const double* Qe
         const double na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
         for (int r = 0; r < 3; r++) a[r] /= na;
         bh /= na;
-        remain = sp_drop_behind(sc, remain & ~(1u << idx), a, bh);
+        remain = sp_drop_behind(sc.obs, remain & ~(1u << idx), a, bh);
         if (n >= SETS_ROWS) return -SETS_TOO_MANY_ROWS;
         for (int c = 0; c < 3; c++) A[3 * n + c] = a[c];
         b[n] = bh;
@@ -537,39 +509,17 @@ BMPC_INL SetResult sets_segment_lane(const SetScene& sc, const double* p0, const
     for (int k = 0; k < 3; k++)
         if (!sp_finite(p0[k]) || !sp_finite(p1[k])) { res.status = SETS_NUMERICAL; return res; }
     sp_init_rows(sc, A, b);
-    unsigned remain = 0;
-    for (int i = 0; i < sc.n_obs; i++) {
-        double out[LP_CRES];
-        loop_closest_pair(sc.A + 3 * SETS_OROWS * i, sc.b + SETS_OROWS * i, sc.AAt + SETS_OROWS * SETS_OROWS * i, sc.nrows[i], nullptr,
-                          p0, p1, out);
-        dist[i * ds] = out[6];
-        remain |= 1u << i;
-    }
-    int n = 6;
-    while (remain) {
-        const int idx = sp_nearest(sc.n_obs, remain, dist, ds);
-        double cp[LP_CRES];
-        loop_closest_pair(sc.A + 3 * SETS_OROWS * idx, sc.b + SETS_OROWS * idx, sc.AAt + SETS_OROWS * SETS_OROWS * idx,
-                          sc.nrows[idx], nullptr, p0, p1, cp);
-        double a[3] = {cp[0] - cp[3], cp[1] - cp[4], cp[2] - cp[5]};
-        double na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-        if (na < 1e-6) {          // the segment touches the obstacle
-            res.collision = 1;
-            for (int k = 0; k < 3; k++) a[k] = cp[k] - p0[k];
-            na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-            if (na < 1e-6) {
-                for (int k = 0; k < 3; k++) a[k] = p1[k] - p0[k];
-                na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-            }
-        }
-        for (int k = 0; k < 3; k++) a[k] /= na;
-        const double bh = a[0] * cp[0] + a[1] * cp[1] + a[2] * cp[2] - 0.001;
-        remain = sp_drop_behind(sc, remain & ~(1u << idx), a, bh);
-        if (n >= SETS_ROWS) { res.status = SETS_TOO_MANY_ROWS; return res; }
-        for (int k = 0; k < 3; k++) A[3 * n + k] = a[k];
-        b[n] = bh;
-        n++;
-    }
+    const LoopScene& ob = sc.obs;
+    double cp[LP_CRES];
+    auto pair = [&](int i) -> const double* {       // computed again when its obstacle is chosen (deterministic), not stored
+        loop_closest_pair(ob.A + 3 * SETS_OROWS * i, ob.b + SETS_OROWS * i, ob.AAt + SETS_OROWS * SETS_OROWS * i, ob.nrows[i], nullptr, p0, p1, cp);
+        return cp;
+    };
+    for (int i = 0; i < ob.n_obs; i++) dist[i * ds] = pair(i)[6];
+    bool touched;
+    const int n = separating_halfspaces(ob, pair, dist, ds, p0, p1, SETS_ROWS, A, b, 6, touched);
+    res.collision = touched;
+    if (n == FS_OVERFLOW) { res.status = SETS_TOO_MANY_ROWS; return res; }
     res.nrows = n;
     double q[9];
     const int st = sp_mvie(A, b, n, false, c, q, res.newton);

@@ -85,22 +85,14 @@ def pack_state(lay, mpc, q, dq, ddq, jerk, qf, v, p_lie):
 
 
 def pack_obstacles(obs_sets, obs_points_sets):
-    """[A, b] polytopes + vertex arrays -> the flat arrays of bmpc_loop_set_obstacles (15 rows / 32 vertices each)."""
-    n = len(obs_sets)
-    if n > 16:
-        raise ValueError("at most 16 scene obstacles")
-    A = np.zeros((n, 15, 3)); b = np.zeros((n, 15)); V = np.zeros((n, 32, 3))
-    nrows = np.zeros(n, np.int32); nv = np.zeros(n, np.int32)
-    for i, ((a_i, b_i), v_i) in enumerate(zip(obs_sets, obs_points_sets)):
-        a_i, b_i, v_i = np.asarray(a_i, float), np.asarray(b_i, float), np.asarray(v_i, float)
-        if a_i.shape[0] > 15 or v_i.shape[0] > 32:
-            raise ValueError("obstacle with more than 15 faces or 32 vertices")
-        A[i, :a_i.shape[0]] = a_i; b[i, :a_i.shape[0]] = b_i; V[i, :v_i.shape[0]] = v_i
-        nrows[i], nv[i] = a_i.shape[0], v_i.shape[0]
-    return A, b, nrows, V, nv
+    """(A, b, nrows, V, nv) of scenes.pack_scene at the device loop's limit: the name earlier callers import."""
+    from .scenes import pack_scene
+    sc = pack_scene(obs_sets, obs_points_sets, MAX_OBS)
+    return sc["A"], sc["b"], sc["nrows"], sc["V"], sc["nv"]
 
 
 MAX_PTS = 8      # LP_MAXPTS of bmpc_loop.hpp: via points of a path
+MAX_OBS = 16     # LP_MAXOBS of bmpc_freespace.hpp: obstacles of a scene
 
 
 def pack_plans(plans):
@@ -185,9 +177,10 @@ class DeviceLoop:
 
     def set_obstacles(self, obs_sets, obs_points_sets):
         """Scene obstacles of ALL rollouts (what BoundMPC.set_obstacle_sets takes per instance on the host)."""
-        A, b, nrows, V, nv = pack_obstacles(obs_sets, obs_points_sets)
-        self._chk(self.lib.bmpc_loop_set_obstacles(self._l, len(obs_sets), self._P(A), self._P(b), nrows.ctypes.data_as(_ip),
-                                                   self._P(V), nv.ctypes.data_as(_ip)), "bmpc_loop_set_obstacles")
+        from .scenes import pack_scene
+        sc = pack_scene(obs_sets, obs_points_sets, MAX_OBS)
+        self._chk(self.lib.bmpc_loop_set_obstacles(self._l, sc["n_obs"], self._P(sc["A"]), self._P(sc["b"]), sc["nrows"].ctypes.data_as(_ip),
+                                                   self._P(sc["V"]), sc["nv"].ctypes.data_as(_ip)), "bmpc_loop_set_obstacles")
 
     def set_scenes(self, scenes, rollout_scene=None):
         """One scene per rollout: `scenes` is a list of (obs_sets, obs_points_sets) pairs as set_obstacles takes them (an empty pair
@@ -196,10 +189,11 @@ class DeviceLoop:
         configuration of the loop: download() / upload() and the records do not carry it."""
         if rollout_scene is not None and len(rollout_scene) != self.R:
             raise ValueError(f"rollout_scene needs one entry per rollout ({self.R})")
-        packed = [pack_obstacles(sets, pts) for sets, pts in scenes]
-        n_obs = np.array([len(p[2]) for p in packed], np.int32)
-        A, b, nrows, V, nv = (np.ascontiguousarray(np.concatenate([p[i] for p in packed])) if packed else np.zeros(0, t)
-                              for i, t in enumerate((float, float, np.int32, float, np.int32)))
+        from .scenes import pack_scene
+        packed = [pack_scene(sets, pts, MAX_OBS) for sets, pts in scenes]
+        n_obs = np.array([p["n_obs"] for p in packed], np.int32)
+        A, b, nrows, V, nv = (np.ascontiguousarray(np.concatenate([p[k] for p in packed])) if packed else np.zeros(0, t)
+                              for k, t in (("A", float), ("b", float), ("nrows", np.int32), ("V", float), ("nv", np.int32)))
         self._chk(self.lib.bmpc_loop_set_scenes(self._l, len(packed), n_obs.ctypes.data_as(_ip), self._P(A), self._P(b), nrows.ctypes.data_as(_ip),
                                                 self._P(V), nv.ctypes.data_as(_ip)), "bmpc_loop_set_scenes")
         if rollout_scene is not None:

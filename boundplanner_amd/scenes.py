@@ -193,3 +193,25 @@ def random_box_scenes(seed, k, n_obs, keep_clear, lo=(-0.3, -0.9, 0.0), hi=(0.9,
             for i in np.nonzero((dist > gap[0]) & (dist < gap[1]))[0][:n_obs - n]:
                 out[s, n] = np.concatenate((c[i] - h[i], c[i] + h[i])); n += 1
     return out
+
+
+def pack_scene(obs_sets, obs_points_sets, max_obs, min_nv=0, pad_empty=False):
+    """Obstacles as the finders hold them ([A, b] polytopes and vertex arrays) as the flat arrays the C entries take
+    (bmpc_loop_set_obstacles / bmpc_loop_set_scenes, bmpc_convex_sets): dict(n_obs, A [n][15][3], b [n][15], nrows [n] int32,
+    V [n][32][3], nv [n] int32), rows and vertices past an obstacle's own zero.  ValueError for more than max_obs obstacles (16 for
+    the device loop, 32 for the set kernel), more than 15 rows or 32 vertices, or fewer than min_nv vertices; with min_nv > 0 every
+    obstacle needs its vertex array.  pad_empty: a scene without obstacles gets arrays of one empty obstacle (nv = 1), so that the
+    pointers handed to the library are never null."""
+    n = len(obs_sets)
+    if n > max_obs or (min_nv > 0 and len(obs_points_sets) != n):
+        raise ValueError(f"at most {max_obs} scene obstacles" + (", one vertex array per obstacle" if min_nv > 0 else ""))
+    m = max(n, 1) if pad_empty else n
+    sc = dict(n_obs=n, A=np.zeros((m, 15, 3)), b=np.zeros((m, 15)), nrows=np.zeros(m, np.int32), V=np.zeros((m, 32, 3)),
+              nv=np.full(m, 1 if n == 0 else 0, np.int32))
+    for i, ((a, b), v) in enumerate(zip(obs_sets, obs_points_sets)):
+        a, b, v = np.asarray(a, float).reshape(-1, 3), np.asarray(b, float).ravel(), np.asarray(v, float).reshape(-1, 3)
+        if a.shape[0] > 15 or not min_nv <= v.shape[0] <= 32:
+            raise ValueError(f"obstacle {i}: at most 15 rows and {min_nv}..32 vertices")
+        sc["A"][i, :a.shape[0]], sc["b"][i, :a.shape[0]], sc["nrows"][i] = a, b, a.shape[0]
+        sc["V"][i, :v.shape[0]], sc["nv"][i] = v, v.shape[0]
+    return sc

@@ -55,20 +55,9 @@ SETS_STATUS = {1: "Ellipse violates constraints", 2: "the set needs more than 20
 
 
 def pack_set_scene(obs_sets, obs_points_sets):
-    """Obstacles as ConvexSetFinder holds them ([A, b] pairs and vertex arrays) in the layout of bmpc_convex_sets: A [n][15][3],
-    b [n][15], nrows [n], V [n][32][3], nv [n] (at most 32 obstacles, 15 rows and 32 vertices each)."""
-    n = len(obs_sets)
-    if n > SETS_MAXOBS or len(obs_points_sets) != n:
-        raise ValueError(f"at most {SETS_MAXOBS} obstacles, one vertex array per obstacle")
-    sc = dict(n_obs=n, A=np.zeros((max(n, 1), SETS_OROWS, 3)), b=np.zeros((max(n, 1), SETS_OROWS)), nrows=np.zeros(max(n, 1), np.int32),
-              V=np.zeros((max(n, 1), SETS_NV, 3)), nv=np.ones(max(n, 1), np.int32))
-    for i, ((a, b), v) in enumerate(zip(obs_sets, obs_points_sets)):
-        a, b, v = np.asarray(a, float).reshape(-1, 3), np.asarray(b, float).ravel(), np.asarray(v, float).reshape(-1, 3)
-        if a.shape[0] > SETS_OROWS or v.shape[0] > SETS_NV or v.shape[0] < 1:
-            raise ValueError(f"obstacle {i}: at most {SETS_OROWS} rows and 1..{SETS_NV} vertices")
-        sc["A"][i, :a.shape[0]], sc["b"][i, :a.shape[0]], sc["nrows"][i] = a, b, a.shape[0]
-        sc["V"][i, :v.shape[0]], sc["nv"][i] = v, v.shape[0]
-    return sc
+    """scenes.pack_scene at the set kernel's limits: the name earlier callers import."""
+    from .scenes import pack_scene
+    return pack_scene(obs_sets, obs_points_sets, SETS_MAXOBS, min_nv=1, pad_empty=True)
 
 
 class BmpcOpts(ctypes.Structure):
@@ -436,7 +425,7 @@ class HipBoundMPC:
 
     def convex_sets_dev(self, scene, e_min, e_max, p0, p1=None, fixed_mid=False, optimize=True, out=None):
         """bmpc_convex_sets_dev on torch tensors of the GPU, enqueued on torch.cuda.current_stream() without waiting.  scene: dict of
-        contiguous GPU tensors in the layout of pack_set_scene (A, b float64; nrows, nv int32; V float64) plus the int n_obs;
+        contiguous GPU tensors in the layout of scenes.pack_scene (A, b float64; nrows, nv int32; V float64) plus the int n_obs;
         e_min / e_max: [3] float64 GPU tensors; p0 / p1: [B,3] float64.  out: dict of preallocated result tensors (the keys of
         convex_sets) or None."""
         import torch

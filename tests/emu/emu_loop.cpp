@@ -31,18 +31,10 @@ extern "C" void emu_loop_prepare_obs(int N, double* S, const double* prev, doubl
     RobotConst rc;
     fill_robot_const(rc);
     const int n_w = 44 * N + 6;
-    std::vector<double> AAt((size_t)n_obs * LP_ROWS * LP_ROWS, 0.0), colres((size_t)6 * n_obs * LP_CRES, 0.0);
-    for (int o = 0; o < n_obs; o++)
-        for (int r = 0; r < nrows[o]; r++)
-            for (int q = 0; q < nrows[o]; q++) {
-                double s = 0;
-                for (int c = 0; c < 3; c++) s += A[45 * o + 3 * r + c] * A[45 * o + 3 * q + c];
-                AAt[(size_t)LP_ROWS * LP_ROWS * o + LP_ROWS * r + q] = s;
-            }
-    std::vector<double> box((size_t)n_obs * 6, 0.0);
-    std::vector<int> is_box(n_obs, 0);
-    for (int o = 0; o < n_obs; o++) is_box[o] = loop_detect_box(A + 45 * o, b + LP_ROWS * o, nrows[o], box.data() + 6 * o, box.data() + 6 * o + 3) ? 1 : 0;
-    LoopScene sc{n_obs, A, b, AAt.data(), nrows, V, nv, box.data(), is_box.data()};
+    std::vector<double> hd((size_t)n_obs * LP_OBS_DOUBLES + 1), colres((size_t)6 * n_obs * LP_CRES, 0.0);
+    std::vector<int> hi((size_t)n_obs * LP_OBS_INTS + 1);
+    loop_pack_obstacles(n_obs, A, b, nrows, V, nv, hd.data(), hi.data());        // the image bmpc_loop_set_obstacles uploads
+    const LoopScene sc = loop_scene_over(n_obs, hd.data(), hi.data());
     for (int pt = 0; pt < 6; pt++)
         for (int ob = 0; ob < n_obs; ob++) loop_collision_pair(&rc, sc, S, pt, ob, colres.data() + (size_t)(pt * n_obs + ob) * LP_CRES);
     for (int i = 0; i < n_w; i++) loop_bound_const(&rc, N, i, lbx + i, ubx + i);

@@ -31,13 +31,14 @@ def prepare(N, S, prev):
 
 
 def prepare_obs(N, S, prev, obs_sets, obs_points_sets):
-    from boundplanner_amd.device_loop import pack_obstacles
-    A, b, nrows, V, nv = pack_obstacles(obs_sets, obs_points_sets)
+    from boundplanner_amd.device_loop import MAX_OBS
+    from boundplanner_amd.scenes import pack_scene
+    sc = pack_scene(obs_sets, obs_points_sets, MAX_OBS)
     ip = ctypes.POINTER(ctypes.c_int)
     n_w = 44 * N + 6
     x0, lbx, ubx, p = np.zeros(n_w), np.zeros(n_w), np.zeros(n_w), np.zeros(875)
-    lib().emu_loop_prepare_obs(N, P(S), P(prev), P(x0), P(lbx), P(ubx), P(p), len(obs_sets), P(A), P(b), nrows.ctypes.data_as(ip),
-                               P(V), nv.ctypes.data_as(ip))
+    lib().emu_loop_prepare_obs(N, P(S), P(prev), P(x0), P(lbx), P(ubx), P(p), sc["n_obs"], P(sc["A"]), P(sc["b"]),
+                               sc["nrows"].ctypes.data_as(ip), P(sc["V"]), sc["nv"].ctypes.data_as(ip))
     return x0, lbx, ubx, p
 
 

@@ -20,11 +20,12 @@ def lib():
 
 def pack_scenes(scenes):
     """[(obs_sets, obs_points_sets), ...] -> n_obs, A, b, nrows, V, nv in the layout of bmpc_loop_set_scenes."""
-    from boundplanner_amd.device_loop import pack_obstacles
-    packed = [pack_obstacles(sets, pts) for sets, pts in scenes]
-    n_obs = np.array([len(p[2]) for p in packed], np.int32)
-    cat = lambda i, t: np.ascontiguousarray(np.concatenate([p[i] for p in packed]), t) if packed else np.zeros(0, t)
-    return n_obs, cat(0, float), cat(1, float), cat(2, np.int32), cat(3, float), cat(4, np.int32)
+    from boundplanner_amd.device_loop import MAX_OBS
+    from boundplanner_amd.scenes import pack_scene
+    packed = [pack_scene(sets, pts, MAX_OBS) for sets, pts in scenes]
+    n_obs = np.array([p["n_obs"] for p in packed], np.int32)
+    cat = lambda k, t: np.ascontiguousarray(np.concatenate([p[k] for p in packed]), t) if packed else np.zeros(0, t)
+    return n_obs, cat("A", float), cat("b", float), cat("nrows", np.int32), cat("V", float), cat("nv", np.int32)
 
 
 def prepare_scenes(N, S, prev, scenes, rollout_scene):

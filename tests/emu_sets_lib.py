@@ -21,8 +21,9 @@ def lib():
 
 def sets(obs_sets, obs_points_sets, e_min, e_max, p0, p1=None, fixed_mid=False, optimize=True, nthreads=8):
     """The dict of HipBoundMPC.convex_sets, computed on the CPU."""
-    from boundplanner_amd.solver import SETS_OUT, out_args, out_arrays, pack_set_scene
-    sc = pack_set_scene(obs_sets, obs_points_sets)
+    from boundplanner_amd.scenes import pack_scene
+    from boundplanner_amd.solver import SETS_MAXOBS, SETS_OUT, out_args, out_arrays
+    sc = pack_scene(obs_sets, obs_points_sets, SETS_MAXOBS, min_nv=1, pad_empty=True)
     p0 = np.ascontiguousarray(p0, float).reshape(-1, 3)
     B = p0.shape[0]
     p1 = None if p1 is None else np.ascontiguousarray(p1, float).reshape(B, 3)

@@ -50,11 +50,12 @@ def main():
     import torch
     from boundplanner_amd import scenes
     from boundplanner_amd.bound_planner import BoundPlanner
-    from boundplanner_amd.solver import HipBoundMPC, default_sets_fn, pack_set_scene
+    from boundplanner_amd.scenes import pack_scene
+    from boundplanner_amd.solver import SETS_MAXOBS, HipBoundMPC, default_sets_fn
     boxes, _, goal_p, goal_r = scenes.example_scene()
     f = BoundPlanner(obstacles=boxes, e_p_max=0.5, seed=7).set_finder
     be = HipBoundMPC(10)
-    sc = pack_set_scene(f.obs_sets, f.obs_points_sets)
+    sc = pack_scene(f.obs_sets, f.obs_points_sets, SETS_MAXOBS, min_nv=1, pad_empty=True)
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     sct = {k: (T(v) if isinstance(v, np.ndarray) else v) for k, v in sc.items()}
     emin, emax = T(np.asarray(f.e_min, float)), T(np.asarray(f.e_max, float))
