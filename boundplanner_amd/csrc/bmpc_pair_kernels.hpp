@@ -694,12 +694,41 @@ BMPC_KBODY void k_pose_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
     RowPre<S_EE, 21> rp_pose;
     rp_pose.load(A, tc, zcur, m.pi);
     const double t_phi = tc[(size_t)S_PHI * A.NP + m.pi], z_phi = zcur[(size_t)S_PHI * A.NP + m.pi];
-    stage_point(A, pg, iw0, k, dc, S);
+    // Three phases (stage_point written out), so that no two of the big states are alive together.  The kinematics hand the pose and
+    // its velocity over -- twelve doubles, pinned: they are finished, and the kinematic columns K, Jl (132 doubles) dead, before the
+    // context exists.  The context (~150 doubles) gives the cost gradient and Hessian and, at once, the PT_SIG fields, its last
+    // readers of Der, er and ep -- stored after the rows they kept those 24 doubles alive through the walk, beside the prefetched row
+    // values (44), Hp, g12 and the PoseAsm accumulators (69).  Then the rows.  (One statement over stage_point, the stores last: the
+    // compiler interleaves kinematics and context, 118 spilled registers; with the hand-over alone 28; with both none.)
+    nat_all(S.zeta, dc, S.y);
+    kin_chain(A.rc, S.y + Z_Q, S.K);
+    kin_jlin(S.K, S.Jl);
+    kin_vel(S.K, S.Jl, S.y + Z_DQ, S.C.v);
+    BMPC_UNROLL
+    for (int a = 0; a < 3; a++) { S.C.pose[a] = S.K.pee[a]; S.C.pose[3 + a] = S.y[Z_PI + a] + 0.5 * dc.dt * S.C.v[3 + a]; }
+    BMPC_UNROLL
+    for (int a = 0; a < 6; a++) { BMPC_PIN(S.C.pose[a]); BMPC_PIN(S.C.v[a]); }
+    seg_ctx_eval(pg, A.N, k, S.y, iw0, S.C);
     double g12[12], Hp[21];
     cost_grad12(pg, S.C, term, g12);
     {
         double HvX[21];
         cost_hess(pg, S.C, term, Hp, HvX);
+    }
+    if (m.valid && A.o.hess == 2) {          // (for k_curv, like the forces below)
+        // what the Gauss-Newton model of r = sig(phi) e leaves out of the Hessian of sig^2 (|e_r|^2 + |e_p|^2)
+        // (casadi_ocp_formulation.py:272-276): 2 sig [ sig'' |e|^2 dphi dphi^T + sig' (ge dphi^T + dphi ge^T) ], ge = De^T e
+        GD Sg = A.part + (size_t)PT_SIG * A.NP + m.pi;
+        const double c2 = 2 * S.C.sig * S.C.dsig;
+        Sg[0] = 2 * S.C.sig * (60.0 * S.C.dsig * (1.0 - 2.0 * S.C.sig)) * S.C.er2ep2;
+        BMPC_UNROLL
+        for (int a = 0; a < 3; a++) Sg[(size_t)(1 + a) * A.NP] = S.C.dpp[a];
+        BMPC_UNROLL
+        for (int bb = 0; bb < 6; bb++) {
+            double ge = S.C.Der[0][bb] * S.C.er[0] + S.C.Der[1][bb] * S.C.er[1] + S.C.Der[2][bb] * S.C.er[2];
+            if (bb < 3) ge += S.C.Dep[0][bb] * S.C.ep[0] + S.C.Dep[1][bb] * S.C.ep[1] + S.C.Dep[2][bb] * S.C.ep[2];
+            Sg[(size_t)(4 + bb) * A.NP] = c2 * ge;
+        }
     }
     RowAcc R;
     R.init(&A, m.pi, m.valid, 0.0, tc, zcur);
@@ -722,19 +751,6 @@ BMPC_KBODY void k_pose_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
         for (int a = 0; a < 3; a++) F[(size_t)a * A.NP] = PO.bpz[a];
         BMPC_UNROLL
         for (int a = 0; a < 6; a++) F[(size_t)(3 + a) * A.NP] = g12[6 + a] + (a >= 3 ? hdt * PO.bpz[a] : 0.0);
-        // what the Gauss-Newton model of r = sig(phi) e leaves out of the Hessian of sig^2 (|e_r|^2 + |e_p|^2)
-        // (casadi_ocp_formulation.py:272-276): 2 sig [ sig'' |e|^2 dphi dphi^T + sig' (ge dphi^T + dphi ge^T) ], ge = De^T e
-        GD Sg = A.part + (size_t)PT_SIG * A.NP + m.pi;
-        const double c2 = 2 * S.C.sig * S.C.dsig;
-        Sg[0] = 2 * S.C.sig * (60.0 * S.C.dsig * (1.0 - 2.0 * S.C.sig)) * S.C.er2ep2;
-        BMPC_UNROLL
-        for (int a = 0; a < 3; a++) Sg[(size_t)(1 + a) * A.NP] = S.C.dpp[a];
-        BMPC_UNROLL
-        for (int bb = 0; bb < 6; bb++) {
-            double ge = S.C.Der[0][bb] * S.C.er[0] + S.C.Der[1][bb] * S.C.er[1] + S.C.Der[2][bb] * S.C.er[2];
-            if (bb < 3) ge += S.C.Dep[0][bb] * S.C.ep[0] + S.C.Dep[1][bb] * S.C.ep[1] + S.C.Dep[2][bb] * S.C.ep[2];
-            Sg[(size_t)(4 + bb) * A.NP] = c2 * ge;
-        }
     }
     GD Pz = A.part + (size_t)PT_POSE * A.NP + m.pi;
     BMPC_UNROLL
@@ -1251,24 +1267,43 @@ BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
     for (int c = 0; c < 3; c++) iw0[c] = lbx[28 * N + (3 + c) * N];
     StagePoint S;
     const int flip = A.st[m.b].flip;
+    // The body in four phases, each with its own inputs, and the four row accumulators carried from one to the next.  (stage_point, G,
+    // the context and ONE walk over all 208 rows kept the kinematic columns (111 doubles), G (42), the context (~150) and both steps
+    // alive together: 169 spilled registers, a third more HBM traffic than the algorithm's.)  The pins are opaque to the compiler and
+    // keep their order among themselves: what is pinned at the end of a phase is finished before the next phase starts, and nothing
+    // of the next phase is computed early.  Row order is that of the single walk -- box, pose, phi and terminal, points -- and no
+    // expression changes, so rp, rdn / rdd and dbar are bitwise what the single walk gave.
+    // ---- 1: the box and non-negativity rows need the natural coordinates and the two steps only ----
     load_zeta(cur_zeta(A, flip), A.NP, m.pi, S.zeta);
-    stage_point(A, pg, iw0, k, dc, S);
-    double G[6][7], g12[12];
-    kin_G(S.K, S.Jl, S.y + Z_DQ, G);
-    cost_grad12(pg, S.C, term, g12);
     double dzt[NZ], dy[NZ];
     load_zeta(A.dz, A.NP, m.pi, dzt);
+    nat_all(S.zeta, dc, S.y);
     nat_all(dzt, dc, dy);
     StepVisitor V;
     V.A = &A; V.pi = m.pi; V.valid = m.valid; V.mu = mu; V.tau = fmax(0.99, 1.0 - mu); V.tc = cur_t(A, flip); V.zc = cur_z(A, flip);
     V.dy = dy; V.dzt = dzt; V.rp = 0.0; V.rdn = 0.0; V.rdd = 1.0; V.dbar = 0.0;
-    double dv[6];
+    walk_rows<StepVisitor, WR_BOX>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    BMPC_PIN(V.rp); BMPC_PIN(V.rdn); BMPC_PIN(V.rdd); BMPC_PIN(V.dbar);
     BMPC_UNROLL
-    for (int a = 0; a < 6; a++) {
-        double s = 0;
+    for (int j = 0; j < 7; j++) BMPC_PIN(S.y[Z_Q + j]);
+    // ---- 2: kinematics (= stage_point up to the pose), contracted at once with the step: G lives in its own scope, and of K only
+    // the six point positions are needed after this phase ----
+    kin_chain(A.rc, S.y + Z_Q, S.K);
+    kin_jlin(S.K, S.Jl);
+    kin_vel(S.K, S.Jl, S.y + Z_DQ, S.C.v);
+    BMPC_UNROLL
+    for (int a = 0; a < 3; a++) { S.C.pose[a] = S.K.pee[a]; S.C.pose[3 + a] = S.y[Z_PI + a] + 0.5 * dc.dt * S.C.v[3 + a]; }
+    double dv[6];
+    {
+        double G[6][7];
+        kin_G(S.K, S.Jl, S.y + Z_DQ, G);
         BMPC_UNROLL
-        for (int j = 0; j < 7; j++) s += G[a][j] * dy[Z_Q + j] + (a < 3 ? S.Jl[a][j] : S.K.zx[j][a - 3]) * dy[Z_DQ + j];
-        dv[a] = s;
+        for (int a = 0; a < 6; a++) {
+            double s = 0;
+            BMPC_UNROLL
+            for (int j = 0; j < 7; j++) s += G[a][j] * dy[Z_Q + j] + (a < 3 ? S.Jl[a][j] : S.K.zx[j][a - 3]) * dy[Z_DQ + j];
+            dv[a] = s;
+        }
     }
     BMPC_UNROLL
     for (int a = 0; a < 3; a++) {
@@ -1279,7 +1314,16 @@ BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
         V.dloc[3 + a] = dy[Z_PI + a] + 0.5 * dc.dt * dv[3 + a];
     }
     point_dirs<0>(S.K, dy + Z_Q, V.dpt);
-    // directional derivative of f
+    BMPC_UNROLL
+    for (int a = 0; a < 6; a++) { BMPC_PIN(dv[a]); BMPC_PIN(V.dloc[a]); BMPC_PIN(S.C.pose[a]); BMPC_PIN(S.C.v[a]); }
+    BMPC_UNROLL
+    for (int c = 0; c < 6; c++)
+        BMPC_UNROLL
+        for (int a = 0; a < 3; a++) BMPC_PIN(V.dpt[c][a]);
+    // ---- 3: reference / error context, directional derivative of f, the pose rows ----
+    seg_ctx_eval(pg, A.N, k, S.y, iw0, S.C);
+    double g12[12];
+    cost_grad12(pg, S.C, term, g12);
     double dphi_f = 0;
     BMPC_UNROLL
     for (int a = 0; a < 6; a++) dphi_f += g12[a] * V.dloc[a] + g12[6 + a] * dv[a];
@@ -1295,7 +1339,10 @@ BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
             double gg = 2 * wts[10] * S.y[Z_D + i] + (i != 4 ? 2 * wts[8] * (pg[P_SLACKS0 + i] + S.y[Z_D + i]) : 0.0);
             dphi_f += gg * dy[Z_D + i];
         }
-    walk_rows(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    walk_rows<StepVisitor, WR_POSE>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    BMPC_PIN(V.rp); BMPC_PIN(V.rdn); BMPC_PIN(V.rdd); BMPC_PIN(V.dbar);
+    // ---- 4: the collision-point rows need the point positions, their directions and the d slacks only ----
+    walk_rows<StepVisitor, WR_PT0 | WR_PT1>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
     if (m.valid) {
         GD P = A.part + m.pi;
         P[PT_DPHIF * A.NP] = dphi_f;
