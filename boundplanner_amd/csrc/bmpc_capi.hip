@@ -653,30 +653,34 @@ extern "C" int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, c
     });
 }
 
-// one super-step's Newton step and line search of B instances from given points, rows and line-search state
-extern "C" int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+// one super-step's Newton step and line search of B instances from given points, rows and line-search state; with want_ctl the
+// iteration-control state is planted (ctl_plant, may be null) and returned (ctl): what the Riccati kernel's control and ls_decide made
+// of it, with the handle's own tol, max_iter, hess_switch, inertia_err, stall_n, gn_backoff, mu_floor_k, dw0
+static int debug_line_search(bmpc_handle* h, const char* name, bool want_ctl, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
                                       const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
                                       double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                                      double* zeta1, double* t1, double* z1, double* ls) {
+                                      double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl) {
     const char* refusal = nullptr;
-    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !dzeta || !dt || !dz || !state || !zeta0 || !t0 || !z0 || !zeta1 || !t1 || !z1 || !ls)
+    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !dzeta || !dt || !dz || !state || !zeta0 || !t0 || !z0 || !zeta1 || !t1 || !z1 || !ls || (want_ctl && !ctl))
         refusal = "bad argument";
     else if ((t == nullptr) != (z == nullptr) || (t == nullptr) != (mode == nullptr)) refusal = "t, z and mode are given together or not at all";
-    else if (!t && (plant0 || plant1)) refusal = "line-search state is planted with given rows only";
+    else if (!t && (plant0 || plant1 || ctl_plant)) refusal = "state is planted with given rows only";
     else if (mode) for (int i = 0; i < B; i++) if (mode[i] < 0 || mode[i] > 2) refusal = "mode must be 0, 1 or 2";
     if (!refusal && h->o.trial_repeats < 9) refusal = "needs a handle whose line search ends inside one launch (trial_repeats >= 9)";
     std::optional<BusyGuard> busy;
-    if (int rc = debug_prologue(h, B, "bmpc_debug_line_search", refusal, busy)) return rc;
+    if (int rc = debug_prologue(h, B, name, refusal, busy)) return rc;
     int np0 = 0, np1 = 0, nls = 0;
     bmpc_pipe_ls_sizes(&np0, &np1, &nls);
+    int npc = 0, nctl = 0;
+    bmpc_pipe_ctl_sizes(&npc, &nctl);
     const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT, nz = B * (N - 1) * NZ;
     double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
     int *iters = nullptr, *status = nullptr;
     Staging s;
     s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
-    s.in(&t, rows); s.in(&z, rows); s.in(&mode, (size_t)B); s.in(&plant0, (size_t)B * np0); s.in(&plant1, (size_t)B * np1);
+    s.in(&t, rows); s.in(&z, rows); s.in(&mode, (size_t)B); s.in(&plant0, (size_t)B * np0); s.in(&plant1, (size_t)B * np1); s.in(&ctl_plant, (size_t)B * npc);
     s.out(&dzeta, nz); s.out(&dt, rows); s.out(&dz, rows); s.out(&state, (size_t)B * 12);
-    s.out(&zeta0, nz); s.out(&t0, rows); s.out(&z0, rows); s.out(&zeta1, nz); s.out(&t1, rows); s.out(&z1, rows); s.out(&ls, (size_t)B * nls);
+    s.out(&zeta0, nz); s.out(&t0, rows); s.out(&z0, rows); s.out(&zeta1, nz); s.out(&t1, rows); s.out(&z1, rows); s.out(&ls, (size_t)B * nls); s.out(&ctl, (size_t)B * nctl);
     s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
     const hipStream_t st = h->stream;
     return s.run(h, st, [&]() -> int {
@@ -684,9 +688,24 @@ extern "C" int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, c
         A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
         A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
         if (int r = pipe_seed(h, A, B, st)) return r;
-        HIPCHK(h, bmpc_pipe_launch_line_search(&A, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0, t0, z0, zeta1, t1, z1, ls, st));
+        HIPCHK(h, bmpc_pipe_launch_line_search(&A, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0, t0, z0, zeta1, t1, z1, ls, st, ctl_plant, ctl));
         return 0;
     });
+}
+
+extern "C" int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                      const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
+                                      double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
+                                      double* zeta1, double* t1, double* z1, double* ls) {
+    return debug_line_search(h, "bmpc_debug_line_search", false, B, x0, lbx, ubx, p, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0, t0, z0,
+                             zeta1, t1, z1, ls, nullptr, nullptr);
+}
+extern "C" int bmpc_debug_iteration_control(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                            const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
+                                            double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
+                                            double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl) {
+    return debug_line_search(h, "bmpc_debug_iteration_control", true, B, x0, lbx, ubx, p, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0,
+                             t0, z0, zeta1, t1, z1, ls, ctl_plant, ctl);
 }
 
 // diagnostic / measurement: HIP events around every launch of the Riccati kernel (bmpc_k_ric: the throughput variant, bmpc_k_ric_lat:

@@ -47,8 +47,10 @@ hipError_t bmpc_pipe_launch_newton_step(bmpc::PipeArgsH* A, const double* d_t, c
 hipError_t bmpc_pipe_launch_line_search(bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode,
                                         const double* d_plant0, const double* d_plant1, double* d_dzeta, double* d_dt, double* d_dz,
                                         double* d_state, double* d_zeta0, double* d_t0, double* d_z0, double* d_zeta1, double* d_t1,
-                                        double* d_z1, double* d_ls, hipStream_t st);
+                                        double* d_z1, double* d_ls, hipStream_t st, const double* d_ctl_plant = nullptr,
+                                        double* d_ctl = nullptr);      // (the last two: bmpc_debug_iteration_control)
 void bmpc_pipe_ls_sizes(int* plant0, int* plant1, int* out);      // doubles per instance: the two planted records, the returned state
+void bmpc_pipe_ctl_sizes(int* plant, int* out);                   // the same of bmpc_debug_iteration_control
 void bmpc_pipe_build_table(int* tbl);
 size_t bmpc_pipe_state_bytes(void);
 

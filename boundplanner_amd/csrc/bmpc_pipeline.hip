@@ -286,21 +286,34 @@ __global__ __launch_bounds__(64) void bmpc_k_dbg_ls_out(PipeArgsH H, double* zet
                                                         double* z1, double* ls) {
     k_ls_out_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GD)zeta0, (GD)t0, (GD)z0, (GD)zeta1, (GD)t1, (GD)z1, (GD)ls);
 }
+// test entry bmpc_debug_iteration_control: the same sequence with the iteration-control state planted per instance before the
+// evaluation launches and copied out after the direction launches and after the trial launch (d_ctl_plant, d_ctl: null = neither)
+__global__ __launch_bounds__(64) void bmpc_k_dbg_ctl_plant(PipeArgsH H, const double* plant) {
+    k_ctl_plant_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)plant);
+}
+__global__ __launch_bounds__(64) void bmpc_k_dbg_ctl_out(PipeArgsH H, double* ctl, int after_trial) {
+    k_ctl_out_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GD)ctl, after_trial);
+}
 extern "C" hipError_t bmpc_pipe_launch_line_search(PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode,
                                                    const double* d_plant0, const double* d_plant1, double* d_dzeta, double* d_dt,
                                                    double* d_dz, double* d_state, double* d_zeta0, double* d_t0, double* d_z0,
-                                                   double* d_zeta1, double* d_t1, double* d_z1, double* d_ls, hipStream_t st) {
+                                                   double* d_zeta1, double* d_t1, double* d_z1, double* d_ls, hipStream_t st,
+                                                   const double* d_ctl_plant, double* d_ctl) {
+    const unsigned nbi = (unsigned)((A->B + 63) / 64);
     const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
     const unsigned nb = (unsigned)((nset + 63) / 64);
     const int nw = waves_for(A->N, A->B);
     if (d_t) hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3(nb), dim3(64), 0, st, *A, d_t, d_z, d_mode);
     if (d_t || d_plant0) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d_plant0, 0, d_t ? 1 : 0);
+    if (d_ctl_plant) hipLaunchKernelGGL(bmpc_k_dbg_ctl_plant, dim3(nbi), dim3(64), 0, st, *A, d_ctl_plant);
     launch_eval(A, nw, st);
     launch_direction(A, A->B, nw, st, nullptr, nullptr, nullptr);
     hipLaunchKernelGGL(bmpc_k_dbg_newton_out, dim3(nb), dim3(64), 0, st, *A, d_dzeta, d_dt, d_dz, d_state);
+    if (d_ctl) hipLaunchKernelGGL(bmpc_k_dbg_ctl_out, dim3(nbi), dim3(64), 0, st, *A, d_ctl, 0);
     if (d_plant1) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d_plant1, 1, 0);
     launch_trial(A, nw, st);
     hipLaunchKernelGGL(bmpc_k_dbg_ls_out, dim3(nb), dim3(64), 0, st, *A, d_zeta0, d_t0, d_z0, d_zeta1, d_t1, d_z1, d_ls);
+    if (d_ctl) hipLaunchKernelGGL(bmpc_k_dbg_ctl_out, dim3(nbi), dim3(64), 0, st, *A, d_ctl, 1);
     return hipGetLastError();
 }
 
@@ -309,4 +322,5 @@ extern "C" int bmpc_pipe_hrec(void) { return HREC; }
 extern "C" int bmpc_pipe_krec(void) { return KREC; }
 extern "C" int bmpc_pipe_npart(void) { return NPART; }
 extern "C" void bmpc_pipe_ls_sizes(int* plant0, int* plant1, int* out) { *plant0 = LS_PLANT0; *plant1 = LS_PLANT1; *out = LS_OUT; }
+extern "C" void bmpc_pipe_ctl_sizes(int* plant, int* out) { *plant = CTL_PLANT; *out = CTL_OUT; }
 extern "C" size_t bmpc_pipe_state_bytes(void) { return sizeof(InstState); }

@@ -6,7 +6,9 @@
 // reference-derived probes of tests/golden/hess_N*.npz.  The second test entry, bmpc_debug_newton_step, shares k_set_rows_body
 // and adds k_newton_out_body, which copies out what the product's own Riccati, forward and row-step kernels left.  The third,
 // bmpc_debug_line_search, adds k_ls_plant_body (line-search state planted per instance, NaN in the copies the trial writes) and
-// k_ls_out_body (the iterate before and after the search, the line-search state).
+// k_ls_out_body (the iterate before and after the search, the line-search state).  The fourth, bmpc_debug_iteration_control, runs
+// the third's sequence with k_ctl_plant_body (iteration-control state planted per instance) and k_ctl_out_body (what the Riccati
+// kernel's control and ls_decide left of it).
 #pragma once
 #include "bmpc_ric_kernel.hpp"
 
@@ -136,6 +138,44 @@ BMPC_INL void k_ls_out_body(const PipeArgs& A, size_t e, GD zeta0, GD t0, GD z0,
         for (int j = 0; j < 8; j++) { const bool in = j < st->nfilt; q[10 + j] = in ? st->filt_th[j] : nan; q[18 + j] = in ? st->filt_phi[j] : nan; }
         q[26] = st->theta_max; q[27] = st->theta_min; q[28] = st->it; q[29] = st->flip; q[30] = st->hess_mode; q[31] = st->state;
         q[32] = st->mu; q[33] = st->filt_mu; q[34] = st->armijo; q[35] = 0.0;
+    }
+}
+
+// Test entry bmpc_debug_iteration_control (tests/test_iteration_control*.py).  Doubles per instance of the planted record and of the
+// returned control state:
+//   plant, before the evaluation launches [CTL_PLANT]: mu, err_prev, err_best, stall, dw_last, gn_back, gn_skip, it
+//   state [CTL_OUT], after the direction launches:     state, status (-1: not finished), mu, hreg, tries, ksel, hess_mode, err_prev,
+//                                                      err_best, stall, dw_last, gn_back, gn_skip, it, fk
+//                    after the trial launch:           it, hess_mode, gn_skip, state; 0
+constexpr int CTL_PLANT = 8, CTL_OUT = 20;
+
+// one thread per instance row, after k_set_rows_body / k_ls_plant_body.  plant [B][CTL_PLANT]: a NaN leaves the field as the init
+// launch (and the mode of k_set_rows_body: hess_mode, err_prev = 0 with mode 2) made it.
+BMPC_INL void k_ctl_plant_body(const PipeArgs& A, size_t e, GCD plant) {
+    if (e >= (size_t)A.B) return;
+    const GST st = A.st + e;                              // slot = row: the pool was filled by the init launch (src[b] = b)
+    GCD q = plant + e * CTL_PLANT;
+    if (q[0] == q[0]) st->mu = q[0];
+    if (q[1] == q[1]) st->err_prev = q[1];
+    if (q[2] == q[2]) st->err_best = q[2];
+    if (q[3] == q[3]) st->stall = (int)q[3];
+    if (q[4] == q[4]) st->dw_last = q[4];
+    if (q[5] == q[5]) st->gn_back = (int)q[5];
+    if (q[6] == q[6]) st->gn_skip = (int)q[6];
+    if (q[7] == q[7]) st->it = (int)q[7];
+}
+
+// one thread per instance row: ctl [B][CTL_OUT]; after_trial = 0 writes entries 0 .. 14, 1 writes 15 .. 19
+BMPC_INL void k_ctl_out_body(const PipeArgs& A, size_t e, GD ctl, int after_trial) {
+    if (e >= (size_t)A.B) return;
+    const GST st = A.st + e;
+    GD q = ctl + (size_t)A.src[e] * CTL_OUT;
+    if (!after_trial) {
+        q[0] = st->state; q[1] = st->state == ST_DONE ? st->status : -1; q[2] = st->mu; q[3] = st->hreg; q[4] = st->tries; q[5] = st->ksel;
+        q[6] = st->hess_mode; q[7] = st->err_prev; q[8] = st->err_best; q[9] = st->stall; q[10] = st->dw_last; q[11] = st->gn_back;
+        q[12] = st->gn_skip; q[13] = st->it; q[14] = st->fk;
+    } else {
+        q[15] = st->it; q[16] = st->hess_mode; q[17] = st->gn_skip; q[18] = st->state; q[19] = 0.0;
     }
 }
 

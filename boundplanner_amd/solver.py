@@ -73,7 +73,7 @@ class BmpcOpts(ctypes.Structure):
 EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error", "bmpc_dims",
            "bmpc_gbounds", "bmpc_solve", "bmpc_solve_dev", "bmpc_solve_dev_async", "bmpc_multipliers_dev", "bmpc_wait", "bmpc_active", "bmpc_fk",
            "bmpc_last_kernel_ms", "bmpc_get_opts", "bmpc_stream", "bmpc_robot_iiwa14", "bmpc_robot_gen3", "bmpc_set_robot", "bmpc_get_robot",
-           "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_stage_matrices", "bmpc_debug_newton_step", "bmpc_debug_line_search", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full",
+           "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_stage_matrices", "bmpc_debug_newton_step", "bmpc_debug_line_search", "bmpc_debug_iteration_control", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full",
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_set_scenes", "bmpc_loop_set_rollout_scenes", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
@@ -138,6 +138,7 @@ def load_library():
         lib.bmpc_debug_stage_matrices.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 8
         lib.bmpc_debug_newton_step.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 4
         lib.bmpc_debug_line_search.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 13
+        lib.bmpc_debug_iteration_control.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 15
         lib.bmpc_debug_time_ric.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.bmpc_debug_ric_stats.argtypes = [ctypes.c_void_p, _dp]
         lib.bmpc_debug_ric_stats_full.argtypes = [ctypes.c_void_p, _dp]
@@ -275,6 +276,10 @@ class HipBoundMPC:
     LS_FIELDS = ("ap", "ad", "D", "phi0", "alpha", "bt", "f0", "th0", "ls0", "nfilt") + tuple(f"filt_th{j}" for j in range(8)) \
         + tuple(f"filt_phi{j}" for j in range(8)) + ("theta_max", "theta_min", "it", "flip", "hess_mode", "state", "mu", "filt_mu", "armijo", "pad")
 
+    CTL_PLANT_FIELDS = ("mu", "err_prev", "err_best", "stall", "dw_last", "gn_back", "gn_skip", "it")
+    CTL_FIELDS = ("state", "status", "mu", "delta_w", "tries", "ksel", "hess_mode", "err_prev", "err_best", "stall", "dw_last", "gn_back",
+                  "gn_skip", "it", "fk", "it_after", "hess_mode_after", "gn_skip_after", "state_after", "pad")
+
     def line_search(self, x0, lbx, ubx, p, t=None, z=None, mode=None, plant0=None, plant1=None):
         """Test entry: Newton step and filter line search of one super-step (bmpc_debug_line_search).  t, z [B][N-1][208] and
         mode [B] as for newton_step, or all None (the rows of the init launch; nothing planted); plant0 [B][22], plant1 [B][19]
@@ -298,6 +303,28 @@ class HipBoundMPC:
         self._chk(self.lib.bmpc_debug_line_search(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z),
                                                   mode.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if mode is not None else None,
                                                   _P(plant0), _P(plant1), *(_P(out[k]) for k in shp)), "bmpc_debug_line_search")
+        return out
+
+    def iteration_control(self, x0, lbx, ubx, p, t, z, mode, ctl_plant=None, plant0=None, plant1=None):
+        """Test entry: the sequence of line_search with the iteration-control state planted (ctl_plant [B][8], CTL_PLANT_FIELDS;
+        NaN = leave the field) and returned: the dict of line_search plus ctl [B][20] (CTL_FIELDS) (bmpc_debug_iteration_control)."""
+        lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
+        x0, lbx, ubx, p, t, z = (np.ascontiguousarray(np.atleast_2d(a) if a.ndim < 2 else a, float) for a in (x0, lbx, ubx, p, t, z))
+        B, N = x0.shape[0], self.N
+        mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
+        assert x0.shape == lbx.shape == ubx.shape == (B, 44 * N + 6) and p.shape == (B, 875) and t.shape == z.shape == (B, N - 1, 208)
+        plants = []
+        for a, n in ((plant0, 22), (plant1, 19), (ctl_plant, 8)):
+            if a is not None:
+                a = np.ascontiguousarray(a, float); assert a.shape == (B, n)
+            plants.append(a)
+        shp = dict(dzeta=(B, N - 1, 41), dt=(B, N - 1, 208), dz=(B, N - 1, 208), state=(B, 12), zeta0=(B, N - 1, 41), t0=(B, N - 1, 208),
+                   z0=(B, N - 1, 208), zeta1=(B, N - 1, 41), t1=(B, N - 1, 208), z1=(B, N - 1, 208), ls=(B, 36), ctl=(B, 20))
+        out = {k: np.zeros(v) for k, v in shp.items()}
+        self._chk(self.lib.bmpc_debug_iteration_control(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z),
+                                                        mode.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _P(plants[0]), _P(plants[1]),
+                                                        *(_P(out[k]) for k in shp if k != "ctl"), _P(plants[2]), _P(out["ctl"])),
+                  "bmpc_debug_iteration_control")
         return out
 
     def time_ric(self, on=True):

@@ -277,6 +277,19 @@ int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double
                            const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
                            double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
                            double* zeta1, double* t1, double* z1, double* ls);
+/* Test entry: the sequence of bmpc_debug_line_search with the iteration-control state of every instance planted before the
+ * evaluation launches and returned -- what decides whether there is another iteration and with which Hessian, barrier parameter
+ * and delta_w (the KKT test, the barrier update and the factorisation attempts of the Riccati kernels; the Hessian choice at the end
+ * of the line search).  tol, max_iter, hess_switch, inertia_err, stall_n, gn_backoff, mu_floor_k, dw0 are the handle's options.
+ *   ctl_plant [B][8] (or NULL; a NaN leaves a field as the init launch and `mode` made it): mu, err_prev, err_best, stall, dw_last,
+ *     gn_back, gn_skip, it (planted after plant0: its iteration counter wins);
+ *   ctl [B][20]: after the direction launches state, status (-1: not finished), mu, delta_w, tries, ksel, hess_mode, err_prev,
+ *     err_best, stall, dw_last, gn_back, gn_skip, it, fk; after the trial launch it, hess_mode, gn_skip, state; 0.
+ * Everything else as bmpc_debug_line_search.  Host pointers; B <= workspace slots; hess = 2.  rc 1 on misuse. */
+int bmpc_debug_iteration_control(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
+                                 const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
+                                 double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
+                                 double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl);
 /* Measurement: from the next solve on, HIP events bracket every launch of the Riccati kernel on the handle's stream
  * (bmpc_debug_time_ric(h, 1)); bmpc_debug_ric_stats then returns for the most recent solve {summed launch durations [ms], launches,
  * instance-iterations} of the throughput variant of that kernel in out6[0..2] and of its latency variant (nearly empty super-steps)

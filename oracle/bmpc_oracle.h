@@ -118,6 +118,10 @@ int bmpc_oracle_newton_system(const bmpc_oracle_opts* o, const double* w, const 
 int bmpc_oracle_trial_point(const bmpc_oracle_opts* o, const double* lbx, const double* ubx, const double* p, const double* zeta0,
                             const double* dzeta, const double* t0, const double* c, double alpha, double* t1, double* f1,
                             double* th1, double* ls1);
+/* the KKT error and the iteration control at a given state, from the functions the solve loop calls: out [12] = dual, prim, cmax,
+ * cmin, zsum, lamsum, nrows, sd, sc, err, status, mu_new (tests/test_iteration_control.py; documented in bmpc_solve.c) */
+int bmpc_oracle_kkt_control(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                            const double* t, const double* z, double mu, int it, double* out);
 int bmpc_oracle_debug_hess(const bmpc_oracle_opts* o, const double* x0, const double* lbx, const double* ubx, const double* p,
                            int k, double zval, double lamval, double* Hout, double* Hfd);
 

@@ -813,8 +813,45 @@ static void row_dirs(const prob_t* pb, stage_t* s, double* adots) {
 
 typedef struct {
     double err, dual, prim, compl, compl_mu, sd, sc, f, theta, avg_compl, min_compl, barrier_logsum;
-    int nrows_total;
+    double sum_lam, sum_z;           /* 1-norms of the adjoint multipliers and of the row multipliers (the scaling's inputs) */
+    int nrows_total, neq;
 } kkt_t;
+
+/* The scaled optimality error (IPOPT's E_0 with s_max = 100) from the pieces kkt_error has gathered: s_d, s_c and err.  Called by
+ * kkt_error, and through it by the solve loop and bmpc_oracle_kkt_control. */
+static void kkt_scaled_error(kkt_t* kk) {
+    const double smax = 100.0;
+    kk->sd = fmax(smax, (kk->sum_lam + kk->sum_z) / (double)(kk->neq + kk->nrows_total)) / smax;
+    kk->sc = fmax(smax, kk->sum_z / (double)kk->nrows_total) / smax;
+    kk->err = fmax(fmax(kk->dual / kk->sd, kk->prim), kk->compl / kk->sc);
+}
+
+/* The termination test of the solve loop at iteration `it`: 0 converged, 1 iteration limit, -1 go on (convergence is tested
+ * first). */
+static int kkt_termination(const bmpc_oracle_opts* o, const kkt_t* kk, int it) {
+    if (kk->err <= o->tol && kk->dual <= 1.0 && kk->prim <= 1e-4 && kk->compl <= 1e-4) return 0;
+    if (it >= o->max_iter) return 1;
+    return -1;
+}
+
+/* monotone Fiacco-McCormick update (IPOPT mu_strategy=monotone, eq. (7)) of the solve loop: the barrier parameter the iteration
+ * goes on with (mu itself when nothing changes) */
+static double barrier_update(const bmpc_oracle_opts* o, const kkt_t* kk, double mu) {
+    double emu = fmax(fmax(kk->dual / kk->sd, kk->prim), kk->compl_mu / kk->sc);
+    while (emu <= o->kappa_eps * mu && mu > o->tol / 10.0) {
+        double mu_before = mu;
+        mu = fmax(o->tol / 10.0, fmin(o->kappa_mu * mu, pow(mu, o->theta_mu)));
+        /* not below the optimality error it was released at (scaled): a barrier parameter far below the error
+         * jams the iterates against rows they have yet to identify as active */
+        if (o->mu_floor_k > 0) {
+            double m2 = fmax(mu, fmin(emu / o->mu_floor_k, 0.1));
+            if (m2 >= mu_before) { mu = mu_before; break; }
+            mu = m2;
+        }
+        emu = fmax(fmax(kk->dual / kk->sd, kk->prim), fmax(kk->compl - mu, 0) / kk->sc);
+    }
+    return mu;
+}
 
 /* adjoint multipliers + IPOPT-style scaled optimality error at the current iterate */
 static void kkt_error(prob_t* pb, kkt_t* kk, double mu) {
@@ -871,14 +908,11 @@ static void kkt_error(prob_t* pb, kkt_t* kk, double mu) {
         theta += fabs(pb->r0[i]);
     }
     neq += 24;
-    double smax = 100.0;
-    kk->sd = fmax(smax, (sum_lam + sum_z) / (double)(neq + nrows)) / smax;
-    kk->sc = fmax(smax, sum_z / (double)nrows) / smax;
     kk->dual = dual; kk->prim = prim; kk->compl = compl; kk->compl_mu = compl_mu;
-    kk->err = fmax(fmax(dual / kk->sd, prim), compl / kk->sc);
+    kk->sum_lam = sum_lam; kk->sum_z = sum_z; kk->nrows_total = nrows; kk->neq = neq;
+    kkt_scaled_error(kk);
     kk->f = f; kk->theta = theta;
     kk->avg_compl = sumc / nrows; kk->min_compl = minc;
-    kk->nrows_total = nrows;
 }
 
 static double merit_parts(prob_t* pb, double* f, double* theta, double* logsum) {
@@ -1139,8 +1173,7 @@ int bmpc_oracle_solve(const bmpc_oracle_opts* o, const double* x0, const double*
             for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
         if (o->verbose)
             printf("it %3d f %.6e err %.2e (d %.2e p %.2e c %.2e) mu %.2e\n", it, kk.f, kk.err, kk.dual, kk.prim, kk.compl, mu);
-        if (kk.err <= o->tol && kk.dual <= 1.0 && kk.prim <= 1e-4 && kk.compl <= 1e-4) { st = 0; break; }
-        if (it >= o->max_iter) { st = 1; break; }
+        { const int term = kkt_termination(o, &kk, it); if (term >= 0) { st = term; break; } }
         if (o->mu_strategy == 0) {
             /* LOQO barrier update (IPOPT mu_oracle=loqo) */
             double xi = kk.min_compl / kk.avg_compl;
@@ -1154,22 +1187,10 @@ int bmpc_oracle_solve(const bmpc_oracle_opts* o, const double* x0, const double*
                 for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
             }
         } else if (o->mu_strategy == 1) {
-            /* monotone Fiacco-McCormick update (IPOPT mu_strategy=monotone, eq. (7)) */
-            double emu = fmax(fmax(kk.dual / kk.sd, kk.prim), kk.compl_mu / kk.sc);
-            int changed = 0;
-            while (emu <= o->kappa_eps * mu && mu > o->tol / 10.0) {
-                double mu_before = mu;
-                mu = fmax(o->tol / 10.0, fmin(o->kappa_mu * mu, pow(mu, o->theta_mu)));
-                /* not below the optimality error it was released at (scaled): a barrier parameter far below the error
-                 * jams the iterates against rows they have yet to identify as active */
-                if (o->mu_floor_k > 0) {
-                    double m2 = fmax(mu, fmin(emu / o->mu_floor_k, 0.1));
-                    if (m2 >= mu_before) { mu = mu_before; break; }
-                    mu = m2;
-                }
-                changed = 1;
-                emu = fmax(fmax(kk.dual / kk.sd, kk.prim), fmax(kk.compl - mu, 0) / kk.sc);
-            }
+            /* monotone Fiacco-McCormick update (barrier_update) */
+            const double mu_new = barrier_update(o, &kk, mu);
+            const int changed = mu_new != mu;
+            mu = mu_new;
             if (changed)
                 for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
         }
@@ -1744,6 +1765,37 @@ int bmpc_oracle_trial_point(const bmpc_oracle_opts* o, const double* lbx, const 
     trial_point(o, &pb, save, alpha, f1, th1, ls1);
     for (int k = 1; k < N; k++) memcpy(t1 + (size_t)(k - 1) * MAXROWS, pb.st[k].t, sizeof(double) * MAXROWS);
     free(save); free(pb.st); free(pb.lbq); free(pb.ubq);
+    return 0;
+}
+
+/* The KKT error and the iteration control of the solve loop at a GIVEN state (tests/test_iteration_control.py): at the point w with
+ * row slacks / multipliers t, z [N-1][MAXROWS] (row order of bmpc_oracle_stage_rows), barrier parameter mu and iteration counter it,
+ * through the functions the loop itself calls -- eval_stage, assemble_stage, kkt_error (kkt_scaled_error), kkt_termination,
+ * barrier_update with o's tol / max_iter / kappa_eps / kappa_mu / theta_mu / mu_floor_k:
+ *   out [12] = dual, prim, cmax, cmin, zsum, lamsum, nrows, sd, sc, err, status (0 / 1 / -1 go on), mu_new (mu when status >= 0). */
+int bmpc_oracle_kkt_control(const bmpc_oracle_opts* o, const double* w, const double* lbx, const double* ubx, const double* p,
+                            const double* t, const double* z, double mu, int it, double* out) {
+    prob_t pb;
+    double pins[40];
+    setup_problem(o, &pb, w, lbx, ubx, p, pins);
+    const int N = pb.N;
+    for (int k = N - 1; k >= 1; k--) eval_stage(&pb, k, 0);
+    for (int k = 1; k < N; k++) {
+        stage_t* s = &pb.st[k];
+        for (int i = 0; i < s->nrows; i++) {
+            s->t[i] = t[(size_t)(k - 1) * MAXROWS + i];
+            s->z[i] = z[(size_t)(k - 1) * MAXROWS + i];
+        }
+    }
+    kkt_t kk;
+    memset(&kk, 0, sizeof kk);
+    for (int k = 1; k < N; k++) assemble_stage(&pb, k, mu);
+    kkt_error(&pb, &kk, mu);
+    const int st = kkt_termination(o, &kk, it);
+    out[0] = kk.dual; out[1] = kk.prim; out[2] = kk.compl; out[3] = kk.min_compl; out[4] = kk.sum_z; out[5] = kk.sum_lam;
+    out[6] = kk.nrows_total; out[7] = kk.sd; out[8] = kk.sc; out[9] = kk.err; out[10] = st;
+    out[11] = st >= 0 ? mu : barrier_update(o, &kk, mu);
+    free(pb.st); free(pb.lbq); free(pb.ubq);
     return 0;
 }
 

@@ -243,3 +243,34 @@ extern "C" int emu_line_search(int N, double dt_, int B, const double* w, const 
     launch(nb, [&](int blk, int l) { k_ls_out_body(R.A, (size_t)blk * 64 + l, zeta0, t0, z0, zeta1, t1, z1, ls); });
     return 0;
 }
+
+// The iteration control of one super-step from a given state (tests/test_iteration_control.py; the bodies of
+// bmpc_debug_iteration_control): emu_line_search's sequence with the given tol, max_iter, mu_floor_k and dw0, the iteration-control state planted
+// after the rows (k_ctl_plant_body; null = nothing) and copied out after k_step and after the trial body (k_ctl_out_body).
+// ric_variant 0: k_ric_body; 1: the speculative pair k_ric_att_body + k_ric_body<RESUME> with three attempts.  The trial body is
+// k_trial_spec_body.
+extern "C" int emu_iteration_control(int N, double dt_, double tol, int max_iter, double mu_floor_k, double dw0, int B, const double* w, const double* lbx, const double* ubx,
+                                     const double* p, const double* t, const double* z, const int* mode, const double* plant0,
+                                     const double* plant1, const double* ctl_plant, int ric_variant, double* dzeta, double* dt, double* dz,
+                                     double* state, double* zeta0, double* t0, double* z0, double* zeta1, double* t1, double* z1, double* ls,
+                                     double* ctl) {
+    if (!t || !z || !mode) return 1;
+    SolverOpts o = default_opts(N, dt_);
+    o.tol = tol; o.max_iter = max_iter; o.mu_floor_k = mu_floor_k; o.dw0 = dw0;
+    Rig R(B, B, 1, o, w, lbx, ubx, p);
+    R.own_outputs();
+    R.init();
+    const int nb = (int)((R.nset() + 63) / 64), nbi = (B + 63) / 64;
+    R.set_rows(t, z, mode);
+    launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant0, 0, 1); });
+    if (ctl_plant) launch(nbi, [&](int blk, int l) { k_ctl_plant_body(R.A, (size_t)blk * 64 + l, ctl_plant); });
+    R.eval(R.nw, false);
+    R.direction(ric_variant == 1);
+    launch(nb, [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
+    launch(nbi, [&](int blk, int l) { k_ctl_out_body(R.A, (size_t)blk * 64 + l, ctl, 0); });
+    if (plant1) launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant1, 1, 0); });
+    R.trial(true);
+    launch(nb, [&](int blk, int l) { k_ls_out_body(R.A, (size_t)blk * 64 + l, zeta0, t0, z0, zeta1, t1, z1, ls); });
+    launch(nbi, [&](int blk, int l) { k_ctl_out_body(R.A, (size_t)blk * 64 + l, ctl, 1); });
+    return 0;
+}

@@ -106,3 +106,26 @@ def line_search(N, w, lbx, ubx, p, t=None, z=None, mode=None, plant0=None, plant
                              *(P(out[k]) for k in out))
     assert rc == 0, rc
     return out
+
+
+def iteration_control(N, w, lbx, ubx, p, t, z, mode, ctl_plant=None, plant0=None, plant1=None, dt=0.1, tol=1e-5, max_iter=100, mu_floor_k=1e4, dw0=1e-4, variant=0):
+    """emu_iteration_control: the bodies of bmpc_debug_iteration_control (same arguments and the same dict as
+    HipBoundMPC.iteration_control, tol, max_iter, mu_floor_k and dw0 being the handle's there); variant 1 runs the speculative pair of Riccati bodies."""
+    lib = ctypes.CDLL(build())
+    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
+    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
+    B = w.shape[0]
+    P = lambda a: a.ctypes.data_as(_dp) if a is not None else None
+    t, z = (np.ascontiguousarray(a, float) for a in (t, z))
+    mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
+    assert t.shape == z.shape == (B, N - 1, 208)
+    plant0, plant1, ctl_plant = (None if a is None else np.ascontiguousarray(a, float) for a in (plant0, plant1, ctl_plant))
+    assert plant0 is None or plant0.shape == (B, 22)
+    assert plant1 is None or plant1.shape == (B, 19)
+    assert ctl_plant is None or ctl_plant.shape == (B, 8)
+    out = {k: np.zeros(v) for k, v in LS_SHAPES(B, N).items()}
+    out["ctl"] = np.zeros((B, 20))
+    rc = lib.emu_iteration_control(N, ctypes.c_double(dt), ctypes.c_double(tol), int(max_iter), ctypes.c_double(mu_floor_k), ctypes.c_double(dw0), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z),
+                                   mode.ctypes.data_as(_ip), P(plant0), P(plant1), P(ctl_plant), variant, *(P(out[k]) for k in out))
+    assert rc == 0, rc
+    return out

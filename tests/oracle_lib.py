@@ -202,6 +202,25 @@ def trial_point(N, lbx, ubx, p, zeta0, dzeta, t0, c, alpha, dt=0.1):
     return t1, f1.value, th1.value, ls1.value
 
 
+KKT_FIELDS = ("dual", "prim", "cmax", "cmin", "zsum", "lamsum", "nrows", "sd", "sc", "err", "status", "mu_new")
+
+
+def kkt_control(N, w, lbx, ubx, p, t, z, mu, it, dt=0.1, tol=1e-5, max_iter=100, mu_floor_k=1e4):
+    """The KKT error and the iteration control of the oracle's solve loop at w for given row (t, z) [N-1][216], barrier parameter
+    and iteration counter (bmpc_oracle_kkt_control): dict of KKT_FIELDS (status -1: the iteration goes on, with mu_new)."""
+    lbx, ubx = _boxes(lbx, ubx)
+    w, lbx, ubx, p, t, z = (np.ascontiguousarray(a, float) for a in (w, lbx, ubx, p, t, z))
+    assert t.shape == z.shape == (N - 1, MAXROWS)
+    o = _opts(N, dt)
+    o.tol, o.max_iter, o.mu_floor_k = tol, max_iter, mu_floor_k
+    out = np.zeros(12)
+    rc = lib().bmpc_oracle_kkt_control(ctypes.byref(o), _P(w), _P(lbx), _P(ubx), _P(p), _P(t), _P(z), ctypes.c_double(mu), int(it), _P(out))
+    assert rc == 0
+    d = dict(zip(KKT_FIELDS, (float(v) for v in out)))
+    d["status"], d["nrows"] = int(out[10]), int(out[6])
+    return d
+
+
 def debug_hess(N, w, lbx, ubx, p, k, zval, lamval, dt=0.1):
     """(analytic, finite-difference) Lagrangian Hessian of stage k without barrier terms (bmpc_oracle_debug_hess)."""
     lbx, ubx = _boxes(lbx, ubx)
