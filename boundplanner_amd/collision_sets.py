@@ -7,12 +7,13 @@ init_halfspaces_point (:400-421) and compute_set_projs_line (:491-510).
 The reference solves, per obstacle polytope {x: A x <= b - 0.001}, the QP
     min_{x, phi in [0,1]} |p0 + phi (p1 - p0) - x|^2   s.t.  A x <= b - 0.001
 with qpOASES through CasADi (third-party, not in this image).  Here the same strictly convex
-QP in (x, phi) is solved by a small dual active-set free method: projected alternating
-minimisation is NOT used because it is only linearly convergent; instead the closest pair is
-found by Dykstra-free exact minimisation over phi (1-D convex, golden section on the distance
-from the segment point to the polytope, each distance being an exact polytope projection by
-active-set enumeration for boxes / a primal active-set QP for general polytopes).
+QP in (x, phi) is solved by exact minimisation over phi (1-D convex: golden section on the distance
+from the segment point to the polytope), each distance being an exact polytope projection: the KKT
+point of an active set that Hildreth's dual coordinate ascent guesses, checked, with an enumeration
+of the active sets of size 1..3 behind it (_project_polytope).
 """
+import itertools
+
 import numpy as np
 
 
@@ -26,28 +27,63 @@ def init_halfspaces_point(p, e_max=0.3):
     return a, b
 
 
-def _project_polytope(A, b, y, iters=60):
-    """Euclidean projection of y onto {x: A x <= b} by a primal active-set method (tiny sizes)."""
-    x = y.copy()
-    viol = A @ x - b
-    if np.all(viol <= 1e-12):
-        return x
-    # Dual coordinate ascent (Hildreth) on lambda >= 0: x = y - A^T lambda; exact for strictly
-    # convex projection QPs and adequate for <= 15 rows.
-    lam = np.zeros(A.shape[0])
+SWEEPS = 100        # Hildreth sweeps for the active-set guess (csrc/bmpc_freespace.hpp: LP_SWEEPS)
+
+
+def _kkt_point(A, b, rows, y):
+    """The KKT point of y on the (1..3) `rows` of {A x <= b} held with equality: x = y - sum lam_k a_k with a_k.x = b_k, one step of
+    iterative refinement included.  None unless it is the projection of y: rows independent, lam_k |a_k| >= -1e-12 and
+    a_r.x - b_r <= 1e-12 |a_r| for every row (csrc/bmpc_freespace.hpp: lp_kkt_point)."""
+    Aw, bw = A[rows], b[rows]
+    G = Aw @ Aw.T
+    if not np.linalg.det(G) > 1e-12 * np.prod(np.diag(G)):
+        return None
+    x, lam = y.copy(), np.zeros(len(rows))
+    for _ in range(2):
+        d = np.linalg.solve(G, Aw @ x - bw)
+        lam += d
+        x = x - Aw.T @ d
+    if np.any(lam * np.sqrt(np.diag(G)) < -1e-12) or np.any(A @ x - b > 1e-12 * np.linalg.norm(A, axis=1)):
+        return None
+    return x
+
+
+def _project_polytope(A, b, y):
+    """Euclidean projection of y onto {x: A x <= b} (tiny sizes: <= 15 rows).
+
+    The projection is x = y - A_W^T lam with the rows W that hold with equality, lam >= 0.  Hildreth's dual coordinate ascent on
+    lam >= 0 only guesses W (the rows it leaves with lam > 0); the answer is the KKT point of those rows in closed form, accepted when
+    it is feasible with no negative multiplier, which makes it the projection.  Hildreth's own iterate is never returned: between
+    two rows at a sharp angle it converges too slowly to be of use.  Where the guess fails, the active sets of size 1, 2, 3 are
+    enumerated; where that finds nothing either, the polytope is empty to rounding: ValueError.  The device states the same in
+    csrc/bmpc_freespace.hpp (lp_project_polytope)."""
+    if np.all(A @ y - b <= 1e-12):
+        return y.copy()
+    n = A.shape[0]
+    lam = np.zeros(n)
     AAt = A @ A.T
     diag = np.maximum(np.diag(AAt), 1e-16)
     Ay = A @ y
-    for _ in range(iters * 20):
+    for _ in range(SWEEPS):
         max_change = 0.0
-        for i in range(A.shape[0]):
+        for i in range(n):
             r = Ay[i] - AAt[i] @ lam - b[i]
             new = max(0.0, lam[i] + r / diag[i])
             max_change = max(max_change, abs(new - lam[i]))
             lam[i] = new
         if max_change < 1e-13:
             break
-    return y - A.T @ lam
+    guess = np.flatnonzero(lam > 0.0)
+    if 1 <= len(guess) <= 3:
+        x = _kkt_point(A, b, guess, y)
+        if x is not None:
+            return x
+    for m in (1, 2, 3):
+        for rows in itertools.combinations(range(n), m):
+            x = _kkt_point(A, b, list(rows), y)
+            if x is not None:
+                return x
+    raise ValueError("closest pair: the obstacle polytope has no point (empty after the 1 mm shrink)")
 
 
 def closest_pair_segment_polytope(A, b, p0, p1):

@@ -97,11 +97,54 @@ inline LoopScene loop_scene_over(size_t n, const double* hd, const int* hi) {
 
 // ---- closest pair segment <-> polytope ----------------------------------------------------------------------
 // The algorithm of the host restatement (boundplanner_amd/collision_sets.py: golden section over the segment parameter, each
-// distance an exact projection by Hildreth's dual coordinate ascent), so that both sides agree to rounding.
+// distance an exact projection onto the polytope), so that both sides agree to rounding.
 //
-// Euclidean projection of y onto {x: A x <= b - 0.001} (collision_sets._project_polytope).  Loops run over the fixed
-// LP_ROWS with an early exit at nr so that, unrolled, Ay / lam stay in registers (static indices)
-BMPC_INL void lp_project_polytope(const double* A, const double* b, const double* AAt, int nr, const double* y, double* x) {
+// The projection of y onto {x: A x <= b - 0.001} is x = y - A_W^T lam with the rows W that hold with equality, lam >= 0: three rows
+// at most in general position.  Hildreth's dual coordinate ascent only GUESSES W (the rows it leaves with lam > 0); the answer is the
+// KKT point of those rows, solved in closed form and accepted when it is feasible with no negative multiplier -- which makes it the
+// projection, whatever the guess was worth.  Hildreth's own iterate is never returned: between two rows at a sharp angle its
+// contraction factor (cos^2 of the angle between them) approaches 1 and it is millimetres off when the sweeps run out.  Where the guess
+// fails (sweeps run out, four rows through one vertex, dependent rows) the active sets of size 1, 2, 3 are enumerated, as sp_project
+// (bmpc_sets.hpp) does for the ellipsoid metric; where that finds nothing either the polytope is empty to rounding and the caller is
+// told (false).  The products are written with fma so that every kernel that inlines this rounds it the same way.
+BMPC_INL double lp_dot3(const double* a, const double* c) { return fma(a[0], c[0], fma(a[1], c[1], a[2] * c[2])); }
+
+constexpr int LP_SWEEPS = 100;   // Hildreth sweeps for the guess; an enumeration costs about as much as 25 (5 rows) .. 400 (15 rows)
+
+// The KKT point of y on the m (1..3) rows i0, i1, i2 held with equality: x = y - sum lam_k a_k with a_k.x = b_k - 0.001, one step of
+// iterative refinement included (the Gram matrix of two rows at 2 degrees has condition 3e3).  True when x is the projection: rows
+// independent, lam_k |a_k| >= -1e-12, a_r.x - (b_r - 0.001) <= 1e-12 |a_r| for every row.
+BMPC_INL bool lp_kkt_point(const double* A, const double* b, int nr, int m, int i0, int i1, int i2, const double* y, double* x) {
+    const double *a0 = A + 3 * i0, *a1 = A + 3 * i1, *a2 = A + 3 * i2;
+    // rows the set does not have count as a unit row orthogonal to the others with residual 0: their multiplier is 0
+    const double g00 = lp_dot3(a0, a0), g11 = m >= 2 ? lp_dot3(a1, a1) : 1.0, g22 = m >= 3 ? lp_dot3(a2, a2) : 1.0;
+    const double g01 = m >= 2 ? lp_dot3(a0, a1) : 0.0, g02 = m >= 3 ? lp_dot3(a0, a2) : 0.0, g12 = m >= 3 ? lp_dot3(a1, a2) : 0.0;
+    const double c00 = fma(g11, g22, -g12 * g12), c01 = fma(g02, g12, -g01 * g22), c02 = fma(g01, g12, -g02 * g11);
+    const double c11 = fma(g00, g22, -g02 * g02), c12 = fma(g01, g02, -g00 * g12), c22 = fma(g00, g11, -g01 * g01);
+    const double det = fma(g00, c00, fma(g01, c01, g02 * c02));
+    if (!(det > 1e-12 * g00 * g11 * g22)) return false;
+    double l0 = 0.0, l1 = 0.0, l2 = 0.0;
+    x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
+    for (int pass = 0; pass < 2; pass++) {
+        const double r0 = lp_dot3(a0, x) - (b[i0] - 0.001), r1 = m >= 2 ? lp_dot3(a1, x) - (b[i1] - 0.001) : 0.0,
+                     r2 = m >= 3 ? lp_dot3(a2, x) - (b[i2] - 0.001) : 0.0;
+        const double d0 = fma(c00, r0, fma(c01, r1, c02 * r2)) / det, d1 = fma(c01, r0, fma(c11, r1, c12 * r2)) / det,
+                     d2 = fma(c02, r0, fma(c12, r1, c22 * r2)) / det;
+        l0 += d0; l1 += d1; l2 += d2;
+        for (int c = 0; c < 3; c++) x[c] -= fma(d0, a0[c], fma(d1, a1[c], d2 * a2[c]));
+    }
+    if (l0 * sqrt(g00) < -1e-12 || l1 * sqrt(g11) < -1e-12 || l2 * sqrt(g22) < -1e-12) return false;
+    for (int r = 0; r < nr; r++) {
+        const double* a = A + 3 * r;
+        if (lp_dot3(a, x) - (b[r] - 0.001) > 1e-12 * sqrt(lp_dot3(a, a))) return false;
+    }
+    return true;
+}
+
+// Euclidean projection of y onto {x: A x <= b - 0.001} (collision_sets._project_polytope); false: no KKT point found, x is not
+// one.  The Hildreth loops run over the fixed LP_ROWS with an early exit at nr so that, unrolled, Ay / lam stay in registers (static
+// indices); the KKT solves read their rows from memory.
+BMPC_INL bool lp_project_polytope(const double* A, const double* b, const double* AAt, int nr, const double* y, double* x) {
     double Ay[LP_ROWS], lam[LP_ROWS];
     bool inside = true;
     BMPC_UNROLL
@@ -113,8 +156,8 @@ BMPC_INL void lp_project_polytope(const double* A, const double* b, const double
         }
     }
     x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
-    if (inside) return;
-    for (int sweep = 0; sweep < 1200; sweep++) {
+    if (inside) return true;
+    for (int sweep = 0; sweep < LP_SWEEPS; sweep++) {
         double max_change = 0.0;
         BMPC_UNROLL
         for (int i = 0; i < LP_ROWS; i++) {
@@ -132,57 +175,70 @@ BMPC_INL void lp_project_polytope(const double* A, const double* b, const double
         }
         if (max_change < 1e-13) break;
     }
+    // the guess: the first three rows with lam > 0, and how many there are
+    int m = 0, i0 = 0, i1 = 0, i2 = 0;
     BMPC_UNROLL
     for (int i = 0; i < LP_ROWS; i++)
-        if (i < nr)
-            for (int c = 0; c < 3; c++) x[c] -= A[3 * i + c] * lam[i];
+        if (i < nr && lam[i] > 0.0) {
+            if (m == 0) i0 = i; else if (m == 1) i1 = i; else if (m == 2) i2 = i;
+            m++;
+        }
+    if (m >= 1 && m <= 3 && lp_kkt_point(A, b, nr, m, i0, i1, i2, y, x)) return true;
+    for (m = 1; m <= 3; m++)
+        for (i0 = 0; i0 < nr; i0++)
+            for (i1 = m >= 2 ? i0 + 1 : i0; i1 < (m >= 2 ? nr : i0 + 1); i1++)
+                for (i2 = m == 3 ? i1 + 1 : i1; i2 < (m == 3 ? nr : i1 + 1); i2++)
+                    if (lp_kkt_point(A, b, nr, m, i0, i1, i2, y, x)) return true;
+    return false;
 }
 
 // distance from the segment point p0 + phi d to the polytope {A x <= b - 0.001}; box != null: the polytope is the
-// axis-aligned box [lo, hi] and its exact projection is a clamp (what Hildreth's iteration converges to)
+// axis-aligned box [lo, hi] and its exact projection is a clamp.  ok is cleared when the projection found no point.
 BMPC_INL double lp_seg_dist(const double* A, const double* b, const double* AAt, int nr, const double* box, const double* p0,
-                            const double* d, double phi, double* x) {
+                            const double* d, double phi, double* x, bool& ok) {
     const double y[3] = {p0[0] + phi * d[0], p0[1] + phi * d[1], p0[2] + phi * d[2]};
     if (box) {
         for (int c = 0; c < 3; c++) x[c] = fmin(fmax(y[c], box[c] + 0.001), box[3 + c] - 0.001);
     } else {
-        lp_project_polytope(A, b, AAt, nr, y, x);
+        if (!lp_project_polytope(A, b, AAt, nr, y, x)) ok = false;
     }
     return sqrt((y[0] - x[0]) * (y[0] - x[0]) + (y[1] - x[1]) * (y[1] - x[1]) + (y[2] - x[2]) * (y[2] - x[2]));
 }
 
-// closest pair segment <-> polytope (collision_sets.closest_pair_segment_polytope); out: x, y = p0 + phi d, distance
+// closest pair segment <-> polytope (collision_sets.closest_pair_segment_polytope); out: x, y = p0 + phi d, distance, phi.  A
+// projection that found no point anywhere on the way makes the distance NaN, which separating_halfspaces reports as FS_NUMERICAL.
 BMPC_DEV void loop_closest_pair(const double* A, const double* b, const double* AAt, int nr, const double* box, const double* p0,
                                 const double* p1, double* out) {
     const double d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
     double x[3], phi = 0.0;
+    bool ok = true;
     if (sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) >= 1e-12) {
         double lo = 0.0, hi = 1.0;
         const double gr = (sqrt(5.0) - 1.0) / 2.0;
         double c = hi - gr * (hi - lo), e = lo + gr * (hi - lo);
-        double fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x), fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x);
+        double fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x, ok), fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x, ok);
         for (int it = 0; it < 80; it++) {
             if (fc < fe) {
                 hi = e; e = c; fe = fc;
                 c = hi - gr * (hi - lo);
-                fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x);
+                fc = lp_seg_dist(A, b, AAt, nr, box, p0, d, c, x, ok);
             } else {
                 lo = c; c = e; fc = fe;
                 e = lo + gr * (hi - lo);
-                fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x);
+                fe = lp_seg_dist(A, b, AAt, nr, box, p0, d, e, x, ok);
             }
         }
         const double pm = 0.5 * (lo + hi);
-        const double f0 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 0.0, x), f1 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 1.0, x),
-                     fm = lp_seg_dist(A, b, AAt, nr, box, p0, d, pm, x);
+        const double f0 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 0.0, x, ok), f1 = lp_seg_dist(A, b, AAt, nr, box, p0, d, 1.0, x, ok),
+                     fm = lp_seg_dist(A, b, AAt, nr, box, p0, d, pm, x, ok);
         // min over (distance, phi) pairs in the order (0, 1, pm): ties go to the smaller phi
         double best = f0; phi = 0.0;
         if (f1 < best) { best = f1; phi = 1.0; }
         if (fm < best || (fm == best && pm < phi)) { best = fm; phi = pm; }
     }
-    const double dist = lp_seg_dist(A, b, AAt, nr, box, p0, d, phi, x);
+    const double dist = lp_seg_dist(A, b, AAt, nr, box, p0, d, phi, x, ok);
     for (int c = 0; c < 3; c++) { out[c] = x[c]; out[3 + c] = p0[c] + phi * d[c]; }
-    out[6] = dist; out[7] = phi;
+    out[6] = ok ? dist : __builtin_nan(""); out[7] = phi;
 }
 
 // ---- greedy nearest-first separating halfspaces (ConvexSetFinder.py:330-375) ----------------------------
@@ -218,14 +274,18 @@ BMPC_INL int sp_nearest(int n_obs, unsigned remain, const double* dist, int ds) 
 // record of obstacle i (loop_closest_pair: point of the obstacle, point of the segment, distance) -- the loop hands back what its
 // closest-pair pass stored, the set kernel computes it again; dist[i * ds]: the distances of those records.  The rows are appended to
 // the n rows already in A [cap][3], b [cap].  Returns the new row count, or FS_OVERFLOW when a row does not fit (the host raises
-// there; rows up to cap are written); touched: the segment touches an obstacle, whose row then points along cp - p0 or p1 - p0.
-constexpr int FS_OVERFLOW = -1;
+// there; rows up to cap are written), or FS_NUMERICAL when a closest pair was not found (distance NaN; no row is written); touched:
+// the segment touches an obstacle, whose row then points along cp - p0 or p1 - p0.
+constexpr int FS_OVERFLOW = -1, FS_NUMERICAL = -2;
 template <class Pair>
 BMPC_INL int separating_halfspaces(const LoopScene& sc, Pair pair, const double* dist, int ds, const double* p0, const double* p1,
                                    int cap, double* A, double* b, int n, bool& touched) {
     touched = false;
     unsigned remain = 0;
-    for (int i = 0; i < sc.n_obs; i++) remain |= 1u << i;
+    for (int i = 0; i < sc.n_obs; i++) {
+        remain |= 1u << i;
+        if (!(dist[i * ds] == dist[i * ds])) return FS_NUMERICAL;
+    }
     while (remain) {
         const int idx = sp_nearest(sc.n_obs, remain, dist, ds);
         const double* cp = pair(idx);

@@ -400,6 +400,7 @@ BMPC_DEV void loop_prepare(const RobotConst* rc, int N, double* S, const double*
             n = separating_halfspaces(*sc, [res](int i) { return res + LP_CRES * i; }, res + 6, LP_CRES, k.pc[j], kf.pc[j], LP_ROWS,
                                       &a[0][0], b, n, touched);
             if (n == FS_OVERFLOW) { S[LS_dead] = 2.0; n = LP_ROWS; }       // more rows than max_set_size: the host raises
+            if (n == FS_NUMERICAL) { S[LS_dead] = 3.0; n = 6; }            // an obstacle without a closest pair (empty to rounding)
         }
         for (int c = 0; c < 3; c++)
             for (int r = 0; r < LP_ROWS; r++) p[P_ASETJ + 45 * j + LP_ROWS * c + r] = (r < n) ? a[r][c] : 0.0;

@@ -520,6 +520,7 @@ BMPC_INL SetResult sets_segment_lane(const SetScene& sc, const double* p0, const
     const int n = separating_halfspaces(ob, pair, dist, ds, p0, p1, SETS_ROWS, A, b, 6, touched);
     res.collision = touched;
     if (n == FS_OVERFLOW) { res.status = SETS_TOO_MANY_ROWS; return res; }
+    if (n == FS_NUMERICAL) { res.status = SETS_NUMERICAL; return res; }
     res.nrows = n;
     double q[9];
     const int st = sp_mvie(A, b, n, false, c, q, res.newton);

@@ -344,7 +344,8 @@ int bmpc_loop_set_obstacles(bmpc_loop* l, int n_obs, const double* A, const doub
  * a rollout range out of range) returns 1 with a message in bmpc_loop_last_error and leaves the loop as it was.
  * The assignment is configuration of the loop, not state of the rollout: it is not part of the state vector, of
  * bmpc_loop_download / bmpc_loop_upload or of the records.  A rollout whose scene needs more than 15 rows in a collision set is
- * frozen (dead = 2) like on the shared scene; the others are not affected.
+ * frozen (dead = 2) like on the shared scene, one with an obstacle that has no closest pair (empty after the 1 mm shrink) likewise
+ * (dead = 3); the others are not affected.
  * Device memory: 3108 bytes per obstacle that exists (A, b, A A^T, V, box), about 50 KB for a scene of 16, plus
  * R * 6 * max n_obs * 64 bytes of closest-pair results. */
 int bmpc_loop_set_scenes(bmpc_loop* l, int n_scenes, const int* n_obs, const double* A, const double* b, const int* nrows,

@@ -9,8 +9,8 @@
 using namespace bmpc;
 
 // Obstacles in the layout of bmpc_loop_set_obstacles.  Rows 6.. of a [15][3], b [15] are written (rows 0..5 are the caller's);
-// returns the row count, or -1 when the rows do not fit 15 (loop_prepare marks the rollout dead there); touched as the set kernel's
-// `collision`.
+// returns the row count, -1 (FS_OVERFLOW) when the rows do not fit 15 or -2 (FS_NUMERICAL) when a closest pair was not found
+// (loop_prepare marks the rollout dead in both); touched as the set kernel's `collision`.
 extern "C" int emu_loop_segment_rows(int n_obs, const double* A, const double* b, const int* nrows, const double* V, const int* nv,
                                      const double* p0, const double* p1, double* a, double* bb, int* touched) {
     std::vector<double> hd((size_t)n_obs * LP_OBS_DOUBLES + 1), res((size_t)n_obs * LP_CRES + 1, 0.0);
@@ -24,5 +24,19 @@ extern "C" int emu_loop_segment_rows(int n_obs, const double* A, const double* b
     bool t;
     const int n = separating_halfspaces(sc, [r](int i) { return r + LP_CRES * i; }, r + 6, LP_CRES, p0, p1, LP_ROWS, a, bb, 6, t);
     *touched = t;
-    return n == FS_OVERFLOW ? -1 : n;
+    return n;
+}
+
+// the closest-pair record of one obstacle {A x <= b} (nr rows, as given: the loop's packing detects an axis-aligned box and clamps,
+// use_box = 0 takes the general path as the set kernel does): x(3), y(3), distance, phi
+extern "C" void emu_closest_pair(int nr, const double* A, const double* b, int use_box, const double* p0, const double* p1, double* out) {
+    const int nv = 0;
+    double A15[45] = {0}, b15[LP_ROWS] = {0}, V[3 * LP_NV] = {0};
+    for (int i = 0; i < 3 * nr; i++) A15[i] = A[i];
+    for (int i = 0; i < nr; i++) b15[i] = b[i];
+    std::vector<double> hd(LP_OBS_DOUBLES);
+    int hi[LP_OBS_INTS];
+    loop_pack_obstacles(1, A15, b15, &nr, V, &nv, hd.data(), hi);
+    const LoopScene sc = loop_scene_over(1, hd.data(), hi);
+    loop_closest_pair(sc.A, sc.b, sc.AAt, nr, use_box && sc.is_box[0] ? sc.box : nullptr, p0, p1, out);
 }
