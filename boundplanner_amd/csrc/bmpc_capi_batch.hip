@@ -178,3 +178,45 @@ extern "C" int bmpc_convex_sets(bmpc_handle* h, const bmpc_sets_opts* o, int n_o
     return sets_run(h, "bmpc_convex_sets", true, o, n_obs, obs_A, obs_b, obs_nrows, obs_V, obs_nv, e_min, e_max, B, p0, p1, A, b, nrows,
                     q_ellipse, centre, rounds, newton, collision, status, h->stream);
 }
+
+// test entry (include/boundmpc.h): the parts of the set growth, one lane per item; host pointers
+extern "C" int bmpc_debug_sets_parts(bmpc_handle* h, int mode, int n_obs, const double* obs_A, const double* obs_b, const int* obs_nrows,
+                                     const double* obs_V, const int* obs_nv, const double* e_min, const double* e_max, int B,
+                                     const double* E, const double* p, const double* rows_A, const double* rows_b, const int* rows_m,
+                                     double* A, double* b, int* nrows, double* q, double* c, int* newton, int* status) {
+    if (!h) return 1;
+    const char* what = "bmpc_debug_sets_parts";
+    const bool poly = mode == 0;
+    const bool ptrs = p && A && b && nrows && q && c && newton && status &&
+                      (poly ? (E && e_min && e_max && (n_obs == 0 || (obs_A && obs_b && obs_nrows && obs_V && obs_nv)))
+                            : (rows_A && rows_b && rows_m));
+    if (mode < 0 || mode > 2 || B < 0 || !ptrs) { h->err = std::string(what) + ": mode must be 0, 1 or 2; null argument or B < 0"; return 1; }
+    if (!poly) n_obs = 0;
+    if (n_obs < 0 || n_obs > SETS_MAXOBS || B > (1 << 24)) { h->err = std::string(what) + ": n_obs must be in [0, 32], B <= 2^24"; return 1; }
+    for (int i = 0; i < n_obs; i++)
+        if (obs_nrows[i] < 0 || obs_nrows[i] > SETS_OROWS || obs_nv[i] < 1 || obs_nv[i] > SETS_NV) {
+            h->err = std::string(what) + ": obstacle " + std::to_string(i) + ": rows must be in [0, 15], vertices in [1, 32]";
+            return 1;
+        }
+    for (int t = 0; !poly && t < B; t++)
+        if (rows_m[t] < 0 || rows_m[t] > SETS_ROWS) { h->err = std::string(what) + ": rows_m must be in [0, 20]"; return 1; }
+    if (B == 0) return 0;
+    WEDGED_FAIL(h);
+    BUSY_OR_FAIL(h, what);
+    HIPCHK(h, hipSetDevice(h->o.device));
+    const double lo[3] = {poly ? e_min[0] : 0.0, poly ? e_min[1] : 0.0, poly ? e_min[2] : 0.0};
+    const double hi[3] = {poly ? e_max[0] : 0.0, poly ? e_max[1] : 0.0, poly ? e_max[2] : 0.0};
+    if (poly) rows_A = rows_b = nullptr, rows_m = nullptr;
+    else E = nullptr;
+    const size_t n = (size_t)B, no = (size_t)n_obs;
+    Staging s;
+    s.in(&obs_A, no * SETS_OROWS * 3); s.in(&obs_b, no * SETS_OROWS); s.in(&obs_nrows, no); s.in(&obs_V, no * SETS_NV * 3); s.in(&obs_nv, no);
+    s.in(&E, n * 9); s.in(&p, n * 3); s.in(&rows_A, n * SETS_ROWS * 3); s.in(&rows_b, n * SETS_ROWS); s.in(&rows_m, n);
+    s.out(&A, n * SETS_ROWS * 3); s.out(&b, n * SETS_ROWS); s.out(&nrows, n); s.out(&q, n * 9); s.out(&c, n * 3); s.out(&newton, n);
+    s.out(&status, n);
+    return s.run(h, h->stream, [&]() -> int {
+        const SetScene sc{n_obs, obs_A, obs_b, obs_nrows, obs_V, obs_nv, nullptr, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+        HIPCHK(h, bmpc_launch_sets_parts(B, mode, &sc, E, p, rows_A, rows_b, rows_m, A, b, nrows, q, c, newton, status, h->stream));
+        return 0;
+    });
+}

@@ -34,6 +34,9 @@ hipError_t bmpc_launch_ik(int B, int log2s, const bmpc::IkOpts* o, const bmpc::R
 hipError_t bmpc_launch_sets(int B, int segment, int fixed_mid, int optimize, const bmpc::SetScene* sc, double* AAt_ws,
                             const double* p0, const double* p1, double* A, double* b, int* nrows, double* q, double* c, int* rounds,
                             int* newton, int* collision, int* status, hipStream_t st);
+hipError_t bmpc_launch_sets_parts(int B, int mode, const bmpc::SetScene* sc, const double* E, const double* p, const double* A_in,
+                                  const double* b_in, const int* m_in, double* A, double* b, int* nrows, double* q, double* c,
+                                  int* newton, int* status, hipStream_t st);      // (bmpc_debug_sets_parts)
 // bmpc_pipeline.hip
 hipError_t bmpc_pipe_launch_init(const bmpc::PipeArgsH* A, int n0, hipStream_t st);
 hipError_t bmpc_pipe_launch_retire_out(const bmpc::PipeArgsH* A, int n_max, hipStream_t st);

@@ -66,3 +66,51 @@ extern "C" hipError_t bmpc_launch_sets(int B, int segment, int fixed_mid, int op
                        optimize, s, p0, p1, A, b, nrows, q, c, rounds, newton, collision, status);
     return hipGetLastError();
 }
+
+// Test entry bmpc_debug_sets_parts (include/boundmpc.h): one lane per item runs ONE part of the set growth, the same inlined functions
+// as bmpc_sets_kernel -- mode 0: sp_polyhedron around p in the given metric E (nrows: the row count, or minus the status);
+// mode 1 / 2: sp_mvie with a fixed / free centre on given rows (copied into the lane's output rows first: that is where the product
+// keeps the rows it inscribes in).
+__global__ __launch_bounds__(SETS_NT) void bmpc_sets_parts_kernel(int B, int mode, SetScene sc, const double* E_, const double* p_,
+                                                                  const double* A_in, const double* b_in, const int* m_in,
+                                                                  double* A_out, double* b_out, int* nrows_out, double* q_out,
+                                                                  double* c_out, int* newton_out, int* status_out) {
+    __shared__ double sdist[SETS_MAXOBS * SETS_NT];
+    const long t = (long)blockIdx.x * SETS_NT + threadIdx.x;
+    if (t >= B) return;
+    double* A = A_out + t * SETS_ROWS * 3;
+    double* b = b_out + t * SETS_ROWS;
+    double c[3] = {p_[3 * t], p_[3 * t + 1], p_[3 * t + 2]};
+    double q[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int n = 0, newton = 0, status = SETS_OK;
+    if (mode == 0) {
+        double E[9], Qe[9];
+        for (int k = 0; k < 9; k++) E[k] = E_[9 * t + k];
+        sp_inv3(E, Qe);
+        n = sp_polyhedron(sc, E, Qe, c, sdist + threadIdx.x, SETS_NT, A, b);
+        if (n < 0) status = -n;
+        for (int k = 0; k < 9; k++) q[k] = Qe[k];
+    } else {
+        n = min(max(m_in[t], 0), SETS_ROWS);
+        for (int i = 0; i < 3 * n; i++) A[i] = A_in[t * SETS_ROWS * 3 + i];
+        for (int i = 0; i < n; i++) b[i] = b_in[t * SETS_ROWS + i];
+        status = sp_mvie(A, b, n, mode == 1, c, q, newton);
+    }
+    for (int i = max(n, 0); i < SETS_ROWS; i++) {
+        A[3 * i] = 0.0; A[3 * i + 1] = 0.0; A[3 * i + 2] = 0.0;
+        b[i] = 0.0;
+    }
+    for (int k = 0; k < 9; k++) q_out[9 * t + k] = q[k];
+    for (int k = 0; k < 3; k++) c_out[3 * t + k] = c[k];
+    nrows_out[t] = n;
+    newton_out[t] = newton;
+    status_out[t] = status;
+}
+
+extern "C" hipError_t bmpc_launch_sets_parts(int B, int mode, const SetScene* sc, const double* E, const double* p, const double* A_in,
+                                             const double* b_in, const int* m_in, double* A, double* b, int* nrows, double* q, double* c,
+                                             int* newton, int* status, hipStream_t st) {
+    hipLaunchKernelGGL(bmpc_sets_parts_kernel, dim3((unsigned)((B + SETS_NT - 1) / SETS_NT)), dim3(SETS_NT), 0, st, B, mode, *sc, E, p,
+                       A_in, b_in, m_in, A, b, nrows, q, c, newton, status);
+    return hipGetLastError();
+}

@@ -45,6 +45,11 @@ BMPC_INL double sp_det3(const double* M) {
     return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
 
+BMPC_INL double sp_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+BMPC_INL void sp_cross(const double* a, const double* b, double* c) {
+    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
 // inverse of a 3x3 matrix through the adjugate; returns the determinant
 BMPC_INL double sp_inv3(const double* M, double* Mi) {
     const double d = sp_det3(M);
@@ -136,7 +141,8 @@ BMPC_INL bool sp_ufeas(const SetScene& sc, int o, const double* E, const double*
 }
 
 // Exact projection of u = 0 onto {u: a'_r . u <= b'_r} (obstacle o seen from p0 through E): the KKT points of the active sets of
-// size 1, then 2, then 3 (unit rows); the nearest feasible one of the smallest size that has one.  The tolerances of feasibility and
+// size 1, then 2, then 3 (unit rows), each solved on the rows themselves by Cramer's rule with one step of refinement (the Gram matrix has
+// the square of their condition); the nearest feasible one of the smallest size that has one.  The tolerances of feasibility and
 // of the multipliers' signs are project_polytope's 1e-10, relative to max(1, |u|): in the first round the rows are scaled by 1e-4 and
 // |u| reaches 1e4, where an absolute 1e-10 is below the rounding of a'.u.
 // Returns the point p0 + E u in world coordinates; false when no KKT point exists (an empty obstacle).
@@ -175,12 +181,23 @@ BMPC_INL bool sp_project(const SetScene& sc, int o, const double* E, const doubl
             for (int j = i + 1; j < nr; j++) {
                 double c[3], bj;
                 if (!sp_urow(sc, o, j, E, p0, c, bj)) continue;
-                const double g11 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2], g12 = a[0] * c[0] + a[1] * c[1] + a[2] * c[2],
-                             g22 = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-                const double det = g11 * g22 - g12 * g12;
-                if (!(fabs(det) > 1e-14)) continue;
-                const double l1 = (-bi * g22 + bj * g12) / det, l2 = (-bj * g11 + bi * g12) / det;
-                const double x[3] = {-l1 * a[0] - l2 * c[0], -l1 * a[1] - l2 * c[1], -l1 * a[2] - l2 * c[2]};
+                // the point of the edge a.x = bi, c.x = bj nearest to 0: x = (bi c x e + bj e x a) / |e|^2 along the edge's
+                // direction e = a x c, and x = -l1 a - l2 c
+                double e[3], ce[3], ea[3];
+                sp_cross(a, c, e);
+                const double ee = sp_dot(e, e);                                  // the Gram determinant of the unit rows
+                if (!(ee > 1e-14)) continue;
+                sp_cross(c, e, ce);
+                sp_cross(e, a, ea);
+                double x[3];
+                for (int q = 0; q < 3; q++) x[q] = (bi * ce[q] + bj * ea[q]) / ee;
+                // (a candidate whose multipliers are negative beyond any rounding is left before the refinement: most are)
+                if (fmin(-sp_dot(x, ce), -sp_dot(x, ea)) / ee < -1e-6 * fmax(1.0, sqrt(sp_dot(x, x)))) continue;
+                {                                                                // one step of refinement
+                    const double ri = bi - sp_dot(a, x), rj = bj - sp_dot(c, x);
+                    for (int q = 0; q < 3; q++) x[q] += (ri * ce[q] + rj * ea[q]) / ee;
+                }
+                const double l1 = -sp_dot(x, ce) / ee, l2 = -sp_dot(x, ea) / ee;
                 const double tol = 1e-10 * fmax(1.0, sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]));
                 if (l1 < -tol || l2 < -tol) continue;
                 if (!sp_ufeas(sc, o, E, p0, x, tol)) continue;
@@ -201,18 +218,23 @@ BMPC_INL bool sp_project(const SetScene& sc, int o, const double* E, const doubl
                 for (int k = j + 1; k < nr; k++) {
                     double e[3], bk;
                     if (!sp_urow(sc, o, k, E, p0, e, bk)) continue;
-                    const double G[9] = {a[0] * a[0] + a[1] * a[1] + a[2] * a[2], a[0] * c[0] + a[1] * c[1] + a[2] * c[2],
-                                         a[0] * e[0] + a[1] * e[1] + a[2] * e[2], 0, c[0] * c[0] + c[1] * c[1] + c[2] * c[2],
-                                         c[0] * e[0] + c[1] * e[1] + c[2] * e[2], 0, 0, e[0] * e[0] + e[1] * e[1] + e[2] * e[2]};
-                    const double Gs[9] = {G[0], G[1], G[2], G[1], G[4], G[5], G[2], G[5], G[8]};
-                    if (!(fabs(sp_det3(Gs)) > 1e-14)) continue;
-                    double Gi[9];
-                    sp_inv3(Gs, Gi);
-                    const double r[3] = {-bi, -bj, -bk};
-                    const double l[3] = {Gi[0] * r[0] + Gi[1] * r[1] + Gi[2] * r[2], Gi[3] * r[0] + Gi[4] * r[1] + Gi[5] * r[2],
-                                         Gi[6] * r[0] + Gi[7] * r[1] + Gi[8] * r[2]};
+                    // the vertex a.x = bi, c.x = bj, e.x = bk by Cramer's rule on the rows themselves (the Gram matrix has the
+                    // square of their condition): x = (bi c x e + bj e x a + bk a x c) / det, and x = -l0 a - l1 c - l2 e
+                    double ce[3], ea[3], ac[3];
+                    sp_cross(c, e, ce);
+                    sp_cross(e, a, ea);
+                    sp_cross(a, c, ac);
+                    const double det = sp_dot(a, ce);
+                    if (!(det * det > 1e-14)) continue;                          // det^2: the Gram determinant of the unit rows
                     double x[3];
-                    for (int q = 0; q < 3; q++) x[q] = -l[0] * a[q] - l[1] * c[q] - l[2] * e[q];
+                    for (int q = 0; q < 3; q++) x[q] = (bi * ce[q] + bj * ea[q] + bk * ac[q]) / det;
+                    if (fmin(-sp_dot(x, ce) / det, fmin(-sp_dot(x, ea) / det, -sp_dot(x, ac) / det)) < -1e-6 * fmax(1.0, sqrt(sp_dot(x, x))))
+                        continue;                                                // (as above: left before the refinement)
+                    {                                                            // one step of refinement
+                        const double ri = bi - sp_dot(a, x), rj = bj - sp_dot(c, x), rk = bk - sp_dot(e, x);
+                        for (int q = 0; q < 3; q++) x[q] += (ri * ce[q] + rj * ea[q] + rk * ac[q]) / det;
+                    }
+                    const double l[3] = {-sp_dot(x, ce) / det, -sp_dot(x, ea) / det, -sp_dot(x, ac) / det};
                     const double tol = 1e-10 * fmax(1.0, sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]));
                     if (l[0] < -tol || l[1] < -tol || l[2] < -tol) continue;
                     if (!sp_ufeas(sc, o, E, p0, x, tol)) continue;
@@ -353,7 +375,16 @@ BMPC_INL bool sp_mvie_newton(const double* A, const double* b, int m, const doub
             H[sp_tri(2, 2)] += t * 0.5 / (x[2] * x[2]);
             H[sp_tri(5, 5)] += t * 0.25 / (x[5] * x[5]);
             double dx[NXV];
-            if (!sp_newton_dir<NXV>(H, g, dx)) return false;
+            if (!sp_newton_dir<NXV>(H, g, dx)) {
+                // H is positive definite, but in a set 1 mm thick its condition reaches 1e16 and a pivot may round to <= 0: once
+                // more with the diagonal raised by 1e-12 of its largest entry (a descent direction still; the line search decides)
+                double hmax = 0.0;
+#pragma unroll
+                for (int k = 0; k < NXV; k++) hmax = fmax(hmax, H[sp_tri(k, k)]);
+#pragma unroll
+                for (int k = 0; k < NXV; k++) H[sp_tri(k, k)] += 1e-12 * hmax;
+                if (!sp_newton_dir<NXV>(H, g, dx)) return false;
+            }
             double dec = 0.0;
 #pragma unroll
             for (int k = 0; k < NXV; k++) dec -= g[k] * dx[k];
@@ -380,7 +411,7 @@ BMPC_INL bool sp_mvie_newton(const double* A, const double* b, int m, const doub
 }
 
 // A strictly interior point of {A x <= b} (unit rows) for the free-centre start: the Chebyshev problem max r s.t. a_i.x + r <= b_i
-// by a log-barrier Newton method on (x, r) from xs with r = min slack - 1, t = 1, 8, ... until m / t < 1e-3: an approximate
+// by a log-barrier Newton method on (x, r) from xs with r = min slack - 1, t = 1, 8, ... until m / t < 1e-3 and r >= m / t: an approximate
 // Chebyshev centre (the host starts at the exact one from an LP; any strictly interior start leads to the same optimum).  c: the point; returns its radius min_i (b_i - a_i.c) / |a_i| (<= 0: none).
 BMPC_INL double sp_interior(const double* A, const double* b, int m, const double* xs, double* c, int& newton) {
     double z[4] = {xs[0], xs[1], xs[2], 0.0};
@@ -396,7 +427,10 @@ BMPC_INL double sp_interior(const double* A, const double* b, int m, const doubl
         }
         return f;
     };
-    for (double t = 1.0; m / t >= 1e-3; t *= 8.0) {
+    // on the central path r(t) >= r* - m / t: the path is followed until m / t < 1e-3 AND r >= m / t, i.e. r >= r* / 2 (a set whose
+    // inradius r* is below 1e-3 would otherwise be left with r < 0 and be reported as having no interior)
+    // -- and left as soon as r + m / t <= 0, which proves r* <= 0: an empty set costs no more stages than it takes to see that
+    for (double t = 1.0; m / t >= 1e-3 || (!(z[3] >= m / t) && z[3] + m / t > 0.0 && t < 1e15); t *= 8.0) {
         for (int it = 0; it < 50; it++) {
             double g[4] = {0.0, 0.0, 0.0, -t}, H[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             for (int i = 0; i < m; i++) {
@@ -431,6 +465,14 @@ BMPC_INL double sp_interior(const double* A, const double* b, int m, const doubl
     for (int i = 0; i < m; i++) {
         const double* a = A + 3 * i;
         r = fmin(r, (b[i] - (a[0] * c[0] + a[1] * c[1] + a[2] * c[2])) / sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]));
+    }
+    if (!(r > 0.0)) {               // the search failed: a start that was strictly interior itself is not lost
+        double rs = __builtin_inf();
+        for (int i = 0; i < m; i++) {
+            const double* a = A + 3 * i;
+            rs = fmin(rs, (b[i] - (a[0] * xs[0] + a[1] * xs[1] + a[2] * xs[2])) / sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]));
+        }
+        if (rs > 0.0) { c[0] = xs[0]; c[1] = xs[1]; c[2] = xs[2]; r = rs; }
     }
     return r;
 }

@@ -29,29 +29,42 @@ def project_polytope(A, b, y):
     if A.shape[0] == 0 or np.all(A @ y - b <= 0):
         return y.copy()
     m = A.shape[0]
+    h = b - A @ y                       # the rows seen from y: A w <= h for w = x - y
     best, best_d = None, np.inf
-    tol = 1e-10
     for k in (1, 2, 3):
         if m < k:
             break
         idx = np.array(list(itertools.combinations(range(m), k)))          # [n][k]
-        Ak, bk = A[idx], b[idx]                                             # [n][k][3], [n][k]
-        G = Ak @ Ak.transpose(0, 2, 1)                                      # Gram matrices [n][k][k]
-        r = Ak @ y - bk                                                     # [n][k]
-        det = np.linalg.det(G)
-        ok = np.abs(det) > 1e-14
+        Ak, hk = A[idx], h[idx]                                             # [n][k][3], [n][k]
+        # The KKT point w = -A_k^T lam of each active set, solved on the rows themselves by Cramer's rule with one step of
+        # refinement (the Gram matrix A_k A_k^T has the square of their condition: in the metric of a long ellipsoid rows that are
+        # orthogonal in the world meet at 1e-3 rad).  W [n][k][3]: the dual vectors, W_i . a_j = det delta_ij
+        if k == 1:
+            det, W = np.ones(len(idx)), Ak
+        elif k == 2:
+            e = np.cross(Ak[:, 0], Ak[:, 1])
+            det = (e * e).sum(axis=1)                                       # the Gram determinant of the unit rows
+            W = np.stack((np.cross(Ak[:, 1], e), np.cross(e, Ak[:, 0])), axis=1)
+        else:
+            W = np.stack((np.cross(Ak[:, 1], Ak[:, 2]), np.cross(Ak[:, 2], Ak[:, 0]), np.cross(Ak[:, 0], Ak[:, 1])), axis=1)
+            det = (Ak[:, 0] * W[:, 0]).sum(axis=1)
+        ok = (det > 1e-14) if k < 3 else (det * det > 1e-14)
         if not ok.any():
             continue
-        lam = np.zeros_like(r)
-        lam[ok] = np.linalg.solve(G[ok], r[ok][..., None])[..., 0]          # multipliers of x = y - A_k^T lam
-        x = y[None, :] - np.einsum("nk,nkc->nc", lam, Ak)
-        feas = ((x @ A.T - b[None, :]).max(axis=1) <= tol) & (lam >= -tol).all(axis=1) & ok
+        det = np.where(ok, det, 1.0)
+        w = np.zeros((len(idx), 3))
+        for _ in range(2):
+            r = hk - np.einsum("nkc,nc->nk", Ak, w)
+            w = w + np.einsum("nk,nkc->nc", r, W) / det[:, None]
+        lam = -np.einsum("nkc,nc->nk", W, w) / det[:, None]                 # multipliers of w = -A_k^T lam
+        d = np.linalg.norm(w, axis=1)
+        tol = 1e-10 * np.maximum(1.0, d)                                    # relative: |w| reaches 1e4 in the first round's metric
+        feas = ((w @ A.T - h[None, :]).max(axis=1) <= tol) & (lam >= -tol[:, None]).all(axis=1) & ok
         if feas.any():
-            d = np.linalg.norm(x - y[None, :], axis=1)
             d[~feas] = np.inf
             j = int(np.argmin(d))
             if d[j] < best_d - 1e-14:
-                best, best_d = x[j], d[j]
+                best, best_d = y + w[j], d[j]
         if best is not None:            # a KKT point of a strictly convex QP is THE solution
             break
     if best is None:

@@ -78,7 +78,8 @@ EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error"
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_set_scenes", "bmpc_loop_set_rollout_scenes", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
            "bmpc_loop_replan", "bmpc_loop_init_rollouts", "bmpc_loop_install_ms",
-           "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev", "bmpc_default_sets_opts", "bmpc_convex_sets", "bmpc_convex_sets_dev"]
+           "bmpc_default_ik_opts", "bmpc_ik", "bmpc_ik_dev", "bmpc_default_sets_opts", "bmpc_convex_sets", "bmpc_convex_sets_dev",
+           "bmpc_debug_sets_parts"]
 
 _lib = None
 
@@ -157,6 +158,8 @@ def load_library():
                                          ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _ip]
         lib.bmpc_convex_sets_dev.argtypes = [ctypes.c_void_p, ctypes.POINTER(BmpcSetsOpts), ctypes.c_int] + [ctypes.c_void_p] * 7 + \
             [ctypes.c_int] + [ctypes.c_void_p] * 12
+        lib.bmpc_debug_sets_parts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _dp, _ip, _dp, _dp, ctypes.c_int,
+                                              _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp, _dp, _ip, _ip]
         _lib = lib
     return _lib
 
@@ -474,6 +477,31 @@ class HipBoundMPC:
                                            ptr(scene["nrows"]), ptr(scene["V"]), ptr(scene["nv"]), ptr(e_min), ptr(e_max), B, ptr(p0),
                                            ptr(p1), *out_args(SETS_OUT, out), torch.cuda.current_stream(p0.device).cuda_stream or None)
         self._chk(rc, "bmpc_convex_sets_dev")
+        return out
+
+    def sets_parts(self, mode, p, E=None, scene=None, rows=None):
+        """Test entry bmpc_debug_sets_parts: one part of the set growth per item.  mode 0: one round of the polyhedron growth around
+        p [B,3] in the metric E [B,3,3], scene = (obs_sets, obs_points_sets, e_min, e_max); mode 1 / 2: the inscribed ellipsoid with
+        the centre fixed at p / free and started from p, rows = (A [B,20,3], b [B,20], m [B]).  Returns dict(A, b, nrows (mode 0: the
+        row count or minus the status), q [B,3,3], c [B,3], newton, status)."""
+        p = np.ascontiguousarray(p, float).reshape(-1, 3)
+        B = p.shape[0]
+        I = lambda a: a.ctypes.data_as(_ip) if a is not None else None
+        sc = dict(n_obs=0, A=None, b=None, nrows=None, V=None, nv=None)
+        e_min = e_max = rA = rb = rm = None
+        if mode == 0:
+            sc = pack_set_scene(scene[0], scene[1])
+            e_min, e_max = (np.ascontiguousarray(e, float).reshape(3) for e in scene[2:])
+            E = np.ascontiguousarray(E, float).reshape(B, 9)
+        else:
+            rA, rb = np.ascontiguousarray(rows[0], float).reshape(B, SETS_ROWS * 3), np.ascontiguousarray(rows[1], float).reshape(B, SETS_ROWS)
+            rm = np.ascontiguousarray(rows[2], np.int32).reshape(B)
+        out = dict(A=np.empty((B, SETS_ROWS, 3)), b=np.empty((B, SETS_ROWS)), nrows=np.empty(B, np.int32), q=np.empty((B, 3, 3)),
+                   c=np.empty((B, 3)), newton=np.empty(B, np.int32), status=np.empty(B, np.int32))
+        rc = self.lib.bmpc_debug_sets_parts(self._h, int(mode), sc["n_obs"], _P(sc["A"]), _P(sc["b"]), I(sc["nrows"]), _P(sc["V"]),
+                                            I(sc["nv"]), _P(e_min), _P(e_max), B, _P(E), _P(p), _P(rA), _P(rb), I(rm), _P(out["A"]),
+                                            _P(out["b"]), I(out["nrows"]), _P(out["q"]), _P(out["c"]), I(out["newton"]), I(out["status"]))
+        self._chk(rc, "bmpc_debug_sets_parts")
         return out
 
 

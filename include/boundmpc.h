@@ -290,6 +290,21 @@ int bmpc_debug_iteration_control(bmpc_handle* h, int B, const double* x0, const 
                                  const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
                                  double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
                                  double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl);
+/* Test entry: ONE part of the set growth of bmpc_convex_sets per item, one GPU thread per item, the same device functions as the
+ * product's kernel (tests/test_set_growth_gpu.py compares them with an exact projection and an optimality certificate).
+ *   mode 0  one round of the polyhedron growth around p [B][3] in a GIVEN metric E [B][9] (symmetric positive definite; the product's
+ *           q_inv = L L^T of the last ellipsoid, 1e-4 I in the first round) in the scene of the obs_ arguments and the workspace box
+ *           (as bmpc_convex_sets): A [B][20][3], b [B][20], nrows [B] = the row count, or minus the status (-1 violates, -2 more than
+ *           20 rows, -4 numerical) with status [B] set alike; q [B][9] = E^-1 as the lane formed it; rows_A, rows_b, rows_m unused.
+ *   mode 1  the inscribed ellipsoid of GIVEN rows rows_A [B][20][3], rows_b [B][20], rows_m [B] in [0, 20] with the centre fixed at
+ *           p: q [B][9] = L L^T, c [B][3] = p, newton [B], status [B] (0, 3 no interior point, 4 numerical); A, b, nrows return the rows.
+ *   mode 2  the same with a free centre, the interior search started from p; c: the centre.  The scene arguments and E are unused in
+ *           modes 1 and 2 (may be NULL / 0).
+ * Host pointers.  rc 1 on misuse. */
+int bmpc_debug_sets_parts(bmpc_handle* h, int mode, int n_obs, const double* obs_A, const double* obs_b, const int* obs_nrows,
+                          const double* obs_V, const int* obs_nv, const double* e_min, const double* e_max, int B, const double* E,
+                          const double* p, const double* rows_A, const double* rows_b, const int* rows_m, double* A, double* b,
+                          int* nrows, double* q, double* c, int* newton, int* status);
 /* Measurement: from the next solve on, HIP events bracket every launch of the Riccati kernel on the handle's stream
  * (bmpc_debug_time_ric(h, 1)); bmpc_debug_ric_stats then returns for the most recent solve {summed launch durations [ms], launches,
  * instance-iterations} of the throughput variant of that kernel in out6[0..2] and of its latency variant (nearly empty super-steps)

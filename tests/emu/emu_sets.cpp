@@ -64,3 +64,20 @@ extern "C" int emu_sets_mvie(int m, const double* A, const double* b, int fixed_
     if (newton) *newton = nw;
     return st;
 }
+
+// One round of the polyhedron growth (sp_polyhedron) around p [3] in a given metric E [9] (symmetric; Qe = E^-1 is formed as the lane
+// forms it): rows A [20][3], b [20].  Returns the row count, minus the set status (-1 violates, -2 too many rows, -4 numerical), or
+// -100 on misuse.
+extern "C" int emu_sets_polyhedron(int n_obs, const double* obs_A, const double* obs_b, const int* obs_nrows, const double* obs_V,
+                                   const int* obs_nv, const double* e_min, const double* e_max, const double* E, const double* p,
+                                   double* A, double* b) {
+    if (n_obs < 0 || n_obs > SETS_MAXOBS) return -100;
+    for (int o = 0; o < n_obs; o++)
+        if (obs_nrows[o] < 0 || obs_nrows[o] > SETS_OROWS || obs_nv[o] < 1 || obs_nv[o] > SETS_NV) return -100;
+    SetScene sc{n_obs, obs_A, obs_b, obs_nrows, obs_V, obs_nv, nullptr, {e_min[0], e_min[1], e_min[2]}, {e_max[0], e_max[1], e_max[2]}};
+    double dist[SETS_MAXOBS], Qe[9];
+    sp_inv3(E, Qe);
+    const int n = sp_polyhedron(sc, E, Qe, p, dist, 1, A, b);
+    for (int i = n < 0 ? 0 : n; i < SETS_ROWS; i++) { A[3 * i] = A[3 * i + 1] = A[3 * i + 2] = 0.0; b[i] = 0.0; }
+    return n;
+}

@@ -59,3 +59,18 @@ def mvie(A, b, fixed_mid=None, start=None):
     st = lib().emu_sets_mvie(A.shape[0], A.ctypes.data_as(_dp), b.ctypes.data_as(_dp), int(fixed_mid is not None),
                              c.ctypes.data_as(_dp), q.ctypes.data_as(_dp), ctypes.byref(nw))
     return q.reshape(3, 3), c, st, nw.value
+
+
+def polyhedron(obs_sets, obs_points_sets, e_min, e_max, E, p):
+    """One round of the polyhedron growth around p in the metric E: (n, A [20][3], b [20]); n < 0: minus the set status."""
+    from boundplanner_amd.scenes import pack_scene
+    from boundplanner_amd.solver import SETS_MAXOBS, SETS_ROWS
+    sc = pack_scene(obs_sets, obs_points_sets, SETS_MAXOBS, min_nv=1, pad_empty=True)
+    E, p, e_min, e_max = (np.ascontiguousarray(v, float) for v in (E, p, e_min, e_max))
+    A, b = np.zeros((SETS_ROWS, 3)), np.zeros(SETS_ROWS)
+    P = lambda a: a.ctypes.data_as(_dp)
+    n = lib().emu_sets_polyhedron(sc["n_obs"], P(sc["A"]), P(sc["b"]), sc["nrows"].ctypes.data_as(_ip), P(sc["V"]),
+                                  sc["nv"].ctypes.data_as(_ip), P(e_min), P(e_max), P(E), P(p), A.ctypes.data_as(_dp), b.ctypes.data_as(_dp))
+    if n == -100:
+        raise ValueError("emu_sets_polyhedron: invalid arguments")
+    return n, A, b
