@@ -122,14 +122,21 @@ BMPC_INL void lp_mat_to_rotvec(const double* M, double* v) {
 
 // extrinsic z-y-x Euler angles (as_euler("zyx")): M = Rx(e2) Ry(e1) Rz(e0)
 BMPC_INL void lp_euler_zyx(const double* M, double* e) {
-    double s = M[2];
-    s = s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s);
-    e[1] = asin(s);
-    e[0] = atan2(-M[1], M[0]);
-    e[2] = atan2(-M[5], M[8]);
+    const double PI = 3.14159265358979323846;
+    // M[2] = sin e1, (M[0], M[1]) = cos e1 (cos e0, -sin e0): the middle angle from both keeps its digits next to +-90 deg,
+    // where asin(M[2]) loses half of them; below 64 deg asin is good to rounding and stays (the bits of every recorded run)
+    e[1] = (fabs(M[2]) < 0.9) ? asin(M[2]) : atan2(M[2], sqrt(M[0] * M[0] + M[1] * M[1]));
+    if (fabs(fabs(e[1]) - 0.5 * PI) <= 1e-7) {
+        // gimbal lock, scipy's window and convention: the third angle is 0 and the first carries the combined rotation
+        // (rows 1, 2 of M are [sin, cos, 0], [-+cos, +-sin, 0] of e0 +- e2); outside the window the two are separate
+        e[0] = atan2(M[3], M[4]);
+        e[2] = 0.0;
+    } else {
+        e[0] = atan2(-M[1], M[0]);
+        e[2] = atan2(-M[5], M[8]);
+    }
     // a half turn comes out as +pi or -pi depending on the SIGN OF A ZERO in M (structural zeros of the padded segments'
     // bases): made deterministic -- +pi -- here and in so3.compute_initial_rot_errors, where the reference's value is a coin flip
-    const double PI = 3.14159265358979323846;
     if (fabs(fabs(e[0]) - PI) < 1e-12) e[0] = PI;
     if (fabs(fabs(e[2]) - PI) < 1e-12) e[2] = PI;
 }

@@ -56,3 +56,13 @@ extern "C" void emu_so3(const double* v, const double* M, double* R_of_v, double
     lp_mat_to_rotvec(M, v_of_M);
     lp_euler_zyx(M, eul_of_M);
 }
+
+// the rest of the orientation block, one helper per call (tests/test_loop_orientation.py)
+extern "C" void emu_jac_inv(const double* ax, double sign, double* J) { lp_jac_inv(ax, sign, J); }
+extern "C" void emu_initial_rot_errors(const double* pr, const double* pr_ref, const double* dpn, const double* br1, const double* br2,
+                                       double* e0, double* epar, double* eo1, double* eo2) {
+    lp_initial_rot_errors(pr, pr_ref, dpn, br1, br2, e0, epar, eo1, eo2);
+}
+extern "C" void emu_integrate_rot_ref(const double* pr_ref, const double* omega, double phi0, double phi1, double* out) {
+    lp_integrate_rot_ref(pr_ref, omega, phi0, phi1, out);
+}

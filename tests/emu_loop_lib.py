@@ -56,3 +56,24 @@ def so3(v, M):
     R, v2, e = np.zeros((3, 3)), np.zeros(3), np.zeros(3)
     lib().emu_so3(P(np.ascontiguousarray(v, float)), P(np.ascontiguousarray(M, float)), P(R), P(v2), P(e))
     return R, v2, e
+
+
+_A = lambda a: np.ascontiguousarray(a, float)
+
+
+def jac_inv(ax, sign):
+    J = np.zeros((3, 3))
+    lib().emu_jac_inv(P(_A(ax)), ctypes.c_double(sign), P(J))
+    return J
+
+
+def initial_rot_errors(pr, pr_ref, dpn, br1, br2):
+    out = [np.zeros(3) for _ in range(4)]
+    lib().emu_initial_rot_errors(P(_A(pr)), P(_A(pr_ref)), P(_A(dpn)), P(_A(br1)), P(_A(br2)), *[P(o) for o in out])
+    return out
+
+
+def integrate_rot_ref(pr_ref, omega, phi0, phi1):
+    out = np.zeros(3)
+    lib().emu_integrate_rot_ref(P(_A(pr_ref)), P(_A(omega)), ctypes.c_double(phi0), ctypes.c_double(phi1), P(out))
+    return out
