@@ -54,7 +54,14 @@ hipError_t bmpc_pipe_launch_line_search(bmpc::PipeArgsH* A, const double* d_t, c
                                         double* d_ctl = nullptr);      // (the last two: bmpc_debug_iteration_control)
 void bmpc_pipe_ls_sizes(int* plant0, int* plant1, int* out);      // doubles per instance: the two planted records, the returned state
 void bmpc_pipe_ctl_sizes(int* plant, int* out);                   // the same of bmpc_debug_iteration_control
+long bmpc_pipe_fixed_launches(void);      // launches of this process that went to a fixed-horizon pair kernel (below)
 void bmpc_pipe_build_table(int* tbl);
+// bmpc_pair_n20.hip, bmpc_pair_n30.hip (bmpc_pair_fixed.hpp): the pair kernels of a super-step compiled for one horizon, slot-major
+// layout.  One launch of kernel `kern` (FX_*) over nb workgroups of nt threads for nw groups of pairs.
+enum { FX_POINTS, FX_POSE, FX_EVAL_MAIN, FX_EVAL_CHAIN, FX_POINTS_POSE, FX_EVAL_CURV_SPLIT, FX_STEP, FX_TRIAL, FX_TRIAL_SPEC };
+typedef void (*bmpc_pair_launcher)(int kern, const bmpc::PipeArgsH* A, int nw, unsigned nb, unsigned nt, size_t lds_bytes, hipStream_t st);
+void bmpc_pair_launch_n20(int kern, const bmpc::PipeArgsH* A, int nw, unsigned nb, unsigned nt, size_t lds_bytes, hipStream_t st);
+void bmpc_pair_launch_n30(int kern, const bmpc::PipeArgsH* A, int nw, unsigned nb, unsigned nt, size_t lds_bytes, hipStream_t st);
 size_t bmpc_pipe_state_bytes(void);
 
 // bmpc_capi.hip, for the device loops of bmpc_loop.hip.  A loop registers with the handle it borrows, so that destroying the

@@ -26,9 +26,15 @@ BMPC_INL void load_zeta(GCD arr, size_t NP, size_t pi, double* z) {
     BMPC_UNROLL
     for (int i = 0; i < NZ; i++) z[i] = arr[(size_t)i * NP + pi];
 }
+template <class AT> BMPC_INL void load_zeta(const AT& A, GCD arr, size_t pi, double* z) {      // (the same through the view's addressing: soa_col)
+    GCD col = soa_col(A, arr, pi);
+    BMPC_UNROLL
+    for (int i = 0; i < NZ; i++) z[i] = col[soa_off(A, (size_t)i * A.NP, pi)];
+}
 
 // kinematics + context at zeta (values only; Jacobian G computed by the caller when needed)
-BMPC_INL void stage_point(const PipeArgs& A, PGP pg, const double* iw0, int k, const DynC dc, StagePoint& S) {
+template <class AT>
+BMPC_INL void stage_point(const AT& A, PGP pg, const double* iw0, int k, const DynC dc, StagePoint& S) {
     nat_all(S.zeta, dc, S.y);
     kin_chain(A.rc, S.y + Z_Q, S.K);
     kin_jlin(S.K, S.Jl);
@@ -183,19 +189,9 @@ BMPC_KBODY void k_init_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
 // ------------------------------------------------------------------------------------------
 // k_eval
 // ------------------------------------------------------------------------------------------
-struct RowAcc {   // row data access (accepting the trial values) + KKT partial sums
-    const PipeArgs* A; size_t pi; bool valid; double ad;
-    GCD tc, zc;                                      // the copies of the slack / multiplier arrays that hold the iterate (cur_t, cur_z)
+struct RowSums {  // KKT partial sums over the rows of a pair (what the row assemblers need of RowAcc, whatever its view of the arguments)
     double cmax, csum, cmin, zsum, prim, nrows;     // f, theta, sum log t of this point: k_trial / k_init
-    BMPC_INL void init(const PipeArgs* A_, size_t pi_, bool valid_, double ad_, GCD tc_, GCD zc_) {
-        A = A_; pi = pi_; valid = valid_; ad = ad_; tc = tc_; zc = zc_;
-        cmax = 0; csum = 0; cmin = 1e300; zsum = 0; prim = 0; nrows = 0;
-    }
-    BMPC_INL void row(int s, double h, double& sg, double& r0, double& r1, double& zz) {
-        size_t o = (size_t)s * A->NP + pi;
-        row_tz(tc[o], zc[o], h, sg, r0, r1, zz);        // read-only here: the accepted trial was made current by the flip bit
-    }
-    // the same with the slack t and the multiplier z of the row already in registers (RowPre)
+    // one row with the slack t and the multiplier z already in registers (RowPre)
     BMPC_INL void row_tz(double t, double z_in, double h, double& sg, double& r0, double& r1, double& zz) {
         zz = z_in;
         r1 = BMPC_RCP(t); sg = zz * r1; r0 = sg * (h + t);
@@ -205,6 +201,20 @@ struct RowAcc {   // row data access (accepting the trial values) + KKT partial 
         nrows += 1.0;
     }
 };
+// AT: the view of the argument block the kernel body runs on (PipeArgs, or PipeArgsN with the strides compile-time constants)
+template <class AT> struct RowAccT : RowSums {   // row data access (accepting the trial values) + KKT partial sums
+    const AT* A; size_t pi; bool valid; double ad;
+    GCD tc, zc;                                      // the copies of the slack / multiplier arrays that hold the iterate (cur_t, cur_z)
+    BMPC_INL void init(const AT* A_, size_t pi_, bool valid_, double ad_, GCD tc_, GCD zc_) {
+        A = A_; pi = pi_; valid = valid_; ad = ad_; tc = tc_; zc = zc_;
+        cmax = 0; csum = 0; cmin = 1e300; zsum = 0; prim = 0; nrows = 0;
+    }
+    BMPC_INL void row(int s, double h, double& sg, double& r0, double& r1, double& zz) {
+        size_t o = (size_t)s * A->NP + pi;
+        row_tz(tc[o], zc[o], h, sg, r0, r1, zz);        // read-only here: the accepted trial was made current by the flip bit
+    }
+};
+typedef RowAccT<PipeArgs> RowAcc;
 
 // Row data (t, z) of the contiguous slots S0 .. S0+CNT-1 and box bounds of the dg positions I0 .. I0+CNT-1, loaded in one
 // batch ahead of their use: a thread that loads them where the row is walked waits one memory round trip per row (the
@@ -212,9 +222,10 @@ struct RowAcc {   // row data access (accepting the trial values) + KKT partial 
 template <int S0_, int CNT_> struct RowPre {
     static constexpr int S0 = S0_, CNT = CNT_;
     double t[CNT_], z[CNT_];
-    BMPC_INL void load(const PipeArgs& A, GCD tc, GCD zc, size_t pi) {
+    template <class AT> BMPC_INL void load(const AT& A, GCD tc, GCD zc, size_t pi) {
+        GCD tb = soa_col(A, tc, pi), zb = soa_col(A, zc, pi);
         BMPC_UNROLL
-        for (int i = 0; i < CNT_; i++) { size_t o = (size_t)(S0_ + i) * A.NP + pi; t[i] = tc[o]; z[i] = zc[o]; }
+        for (int i = 0; i < CNT_; i++) { size_t o = soa_off(A, (size_t)(S0_ + i) * A.NP, pi); t[i] = tb[o]; z[i] = zb[o]; }
     }
 };
 template <int I0_, int CNT_> struct BndPre {
@@ -230,8 +241,8 @@ template <int I0_, int CNT_> struct BndPre {
     }
 };
 
-struct PointAsm {
-    RowAcc* R; const KinT* K;
+template <class AT> struct PointAsmT {
+    RowAccT<AT>* R; const KinT* K;
     double M3[6], mc[3], sc, b30[3], b31[3], b3z[3], bc0, bc1, bcz;
     double Hqq[28], gq0[7], gq1[7], gqz[7], dD[6], gD0[6], gD1[6], gDz[6], cd[6][7], Fc[6][3];
     double pt[15], pz[15];        // row data of the current point's 15 slots, loaded in one batch (see RowPre)
@@ -243,10 +254,11 @@ struct PointAsm {
     }
     BMPC_INL void skip(int) {}
     template <int C> BMPC_INL void point_begin(unsigned act) {
+        GCD tb = soa_col(*R->A, R->tc, R->pi), zb = soa_col(*R->A, R->zc, R->pi);
         BMPC_UNROLL
         for (int i = 0; i < 15; i++) {       // (row data of constraint rows only)
-            size_t o = (size_t)(S_COL + 15 * C + i) * R->A->NP + R->pi;
-            if ((act >> i) & 1u) { pt[i] = R->tc[o]; pz[i] = R->zc[o]; } else { pt[i] = 1.0; pz[i] = 0.0; }
+            size_t o = soa_off(*R->A, (size_t)(S_COL + 15 * C + i) * R->A->NP, R->pi);
+            if ((act >> i) & 1u) { pt[i] = tb[o]; pz[i] = zb[o]; } else { pt[i] = 1.0; pz[i] = 0.0; }
         }
         BMPC_UNROLL
         for (int i = 0; i < 6; i++) M3[i] = 0;
@@ -294,6 +306,7 @@ struct PointAsm {
         for (int a = 0; a < 3; a++) Fc[C][a] = b3z[a];
     }
 };
+typedef PointAsmT<PipeArgs> PointAsm;
 
 // results of k_points for one pair, loaded from the side array where they are needed
 struct PointRes {
@@ -326,7 +339,7 @@ struct PointRes {
 };
 
 struct PoseAsm {
-    RowAcc* R;
+    RowSums* R;
     double M6[21], mS[3][6], sS[3], bp0[6], bp1[6], bpz[6], bS0[3], bS1[3], bSz[3];
     BMPC_INL void init(const double* Hp, const double* g12) {
         BMPC_UNROLL
@@ -439,7 +452,7 @@ BMPC_INL void walk_diag_pos(const RP& rp, const BP& bp, int k, const double* y, 
 }
 
 struct DiagAsm {
-    RowAcc* R;
+    RowSums* R;
     double D, g0, g1, gz;
     BMPC_INL void begin() { D = 0; g0 = 0; g1 = 0; gz = 0; }
     BMPC_INL void diag(double coef, double h, double t, double z) {
@@ -504,9 +517,9 @@ BMPC_INL void chain_all(const KinT& K, const double Jl[3][7], const double G[6][
 }
 // P17 blocks: for position I of the (q, dq, pi) block emit the three slack-column couplings, then
 // D, g0, g1, gz of that position (its diagonal rows are walked here), 7 fields
-template <int I, int IEND, class RP, class BP, class EM>
-BMPC_INL void p17_emit_all(const PipeArgs& A, PGP pg, const RP& rp, const BP& bp, int k, const double* y, const KinT& K,
-                           const double Jl[3][7], const double G[6][7], double hdt, RowAcc& R, const PointRes& PA,
+template <int I, int IEND, class AT, class RP, class BP, class EM>
+BMPC_INL void p17_emit_all(const AT& A, PGP pg, const RP& rp, const BP& bp, int k, const double* y, const KinT& K,
+                           const double Jl[3][7], const double G[6][7], double hdt, RowSums& R, const PointRes& PA,
                            const PoseAsm& P, const double* bv, EM& E) {
     if constexpr (I < IEND) {
         PGP wts = pg + P_W;
@@ -626,9 +639,9 @@ BMPC_INL void curvature_emit(const KinT& K, const double Jl[3][7], const double*
 }
 
 // DG entries: position I of the dg order
-template <int I, class RP, class BP, class EM>
-BMPC_INL void dg_emit_all(const PipeArgs& A, PGP pg, const RP& rp, const BP& bp, int k, bool term,
-                          const double* y, RowAcc& R, const PointRes& PA, const PoseAsm& PO, EM& E) {
+template <int I, class AT, class RP, class BP, class EM>
+BMPC_INL void dg_emit_all(const AT& A, PGP pg, const RP& rp, const BP& bp, int k, bool term,
+                          const double* y, RowSums& R, const PointRes& PA, const PoseAsm& PO, EM& E) {
     if constexpr (I < 38) {
         PGP wts = pg + P_W;
         DiagAsm dgv;
@@ -674,7 +687,8 @@ BMPC_INL void dg_emit_all(const PipeArgs& A, PGP pg, const RP& rp, const BP& bp,
 // (111) together with the accumulators do not fit one wavefront's register file; neither kernel needs the other's big state.
 // lds: staged parameter vectors only.
 // ------------------------------------------------------------------------------------------
-BMPC_KBODY void k_pose_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par) {
+template <class AT>
+BMPC_KBODY void k_pose_body(const AT& A, int wave, int lane, LDSD* lds_par) {
     const int count = A.L.cnt[0], N = A.N;
     if (wave * ipw_of(N) >= count) return;
     PairMap m = pair_map(A, A.L.eval, count, wave, lane);
@@ -689,7 +703,7 @@ BMPC_KBODY void k_pose_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
     StagePoint S;
     const int flip = A.st[m.b].flip;
     GCD zc = cur_zeta(A, flip), tc = cur_t(A, flip), zcur = cur_z(A, flip);
-    load_zeta(zc, A.NP, m.pi, S.zeta);
+    load_zeta(A, zc, m.pi, S.zeta);
     // row data of the pose rows: in flight while the kinematics are evaluated
     RowPre<S_EE, 21> rp_pose;
     rp_pose.load(A, tc, zcur, m.pi);
@@ -730,7 +744,7 @@ BMPC_KBODY void k_pose_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
             Sg[(size_t)(4 + bb) * A.NP] = c2 * ge;
         }
     }
-    RowAcc R;
+    RowAccT<AT> R;
     R.init(&A, m.pi, m.valid, 0.0, tc, zcur);
     // (KKT partial sums of the pose rows only: k_points runs beside this kernel, k_eval combines the two)
     PoseAsm PO;
@@ -778,8 +792,8 @@ BMPC_KBODY void k_pose_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
 // launch costs its single-thread latency, in the bulk regime the two lighter bodies spill less --: MODE 1 everything but the chained (q, dq, pi) block -- a third of the arithmetic, with no row of its own (no KKT partial
 // sum depends on it) --, MODE 2 that block alone, straight into the record.  Same expressions entry for entry, and the library is
 // built with -ffp-contract=on (contraction per source expression, whatever else the surrounding body computes): bitwise the record of MODE 0.
-template <int MODE>
-BMPC_KBODY void k_eval_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
+template <int MODE, class AT>
+BMPC_KBODY void k_eval_body(const AT& A, int wave, int lane, LDSD* lds) {
     const int count = A.L.cnt[0], N = A.N;
     if (wave * ipw_of(N) >= count) return;
     PairMap m = pair_map(A, A.L.eval, count, wave, lane);
@@ -792,7 +806,7 @@ BMPC_KBODY void k_eval_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
     if constexpr (MODE == 2) {
         struct { double zeta[NZ], y[NZ]; KinT K; double Jl[3][7]; } S;
         const int flip = A.st[m.b].flip;
-        load_zeta(cur_zeta(A, flip), A.NP, m.pi, S.zeta);
+        load_zeta(A, cur_zeta(A, flip), m.pi, S.zeta);
         nat_all(S.zeta, dc, S.y);
         kin_chain(A.rc, S.y + Z_Q, S.K);
         kin_jlin(S.K, S.Jl);
@@ -819,13 +833,13 @@ BMPC_KBODY void k_eval_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
     struct { double zeta[NZ], y[NZ]; KinT K; double Jl[3][7]; } S;
     const int flip = A.st[m.b].flip;
     GCD zc = cur_zeta(A, flip), tc = cur_t(A, flip), zcur = cur_z(A, flip);
-    load_zeta(zc, A.NP, m.pi, S.zeta);
+    load_zeta(A, zc, m.pi, S.zeta);
     nat_all(S.zeta, dc, S.y);
     kin_chain(A.rc, S.y + Z_Q, S.K);
     kin_jlin(S.K, S.Jl);
     double G[6][7];
     kin_G(S.K, S.Jl, S.y + Z_DQ, G);
-    RowAcc R;
+    RowAccT<AT> R;
     R.init(&A, m.pi, m.valid, ad, tc, zcur);
     // ---- results of k_pose (pose-space Hessian, slack couplings, gradients): loaded phase by phase, right before their use ----
     PoseAsm PO;
@@ -924,7 +938,7 @@ BMPC_KBODY void k_eval_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
     // through the chained block: there the register file is needed for the kinematic columns (K, Jl, G), which the register
     // allocator otherwise parks in scratch memory and reloads for every entry of the block
     double zeta2[NZ], y2[NZ];
-    load_zeta(zc, A.NP, m.pi, zeta2);
+    load_zeta(A, zc, m.pi, zeta2);
     nat_all(zeta2, dc, y2);
     // ---- remaining diagonal rows + gradients: ddq, u, rs, drs, ps, dps, d ----
     RowPre<28, 40> rp_b;                     // rows + bounds of the ddq, u box, the slack rows, the zeta-diagonal rows
@@ -992,7 +1006,8 @@ BMPC_KBODY void k_eval_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
 // A kernel of its own because together with the pose / chain work of k_eval it does not fit the
 // register file (the spills were what bound k_eval).
 // ------------------------------------------------------------------------------------------
-BMPC_KBODY void k_points_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par) {
+template <class AT>
+BMPC_KBODY void k_points_body(const AT& A, int wave, int lane, LDSD* lds_par) {
     const int count = A.L.cnt[0], N = A.N;
     if (wave * ipw_of(N) >= count) return;
     PairMap m = pair_map(A, A.L.eval, count, wave, lane);
@@ -1005,19 +1020,19 @@ BMPC_KBODY void k_points_body(const PipeArgs& A, int wave, int lane, LDSD* lds_p
     PGP pg = stage_params(A, A.L.eval, count, wave, lane, m, lds_par);
     double zeta[NZ], y[NZ];
     const int flip = A.st[m.b].flip;
-    load_zeta(cur_zeta(A, flip), A.NP, m.pi, zeta);
+    load_zeta(A, cur_zeta(A, flip), m.pi, zeta);
     nat_all(zeta, dc, y);
     KinT K;
     kin_chain(A.rc, y + Z_Q, K);
     SegCtx C;
     BMPC_UNROLL
     for (int i = 0; i < 6; i++) C.sl[i] = pg[P_SLACKS0 + i] + y[Z_D + i];
-    RowAcc R;
+    RowAccT<AT> R;
     R.init(&A, m.pi, m.valid, 0.0, cur_t(A, flip), cur_z(A, flip));
-    PointAsm PA;
+    PointAsmT<AT> PA;
     PA.R = &R; PA.K = &K;
     PA.init();
-    walk_points<PointAsm, 0>(pg, K, C.sl, PA);
+    walk_points<PointAsmT<AT>, 0>(pg, K, C.sl, PA);
     if (!m.valid) return;
     GD Sd = A.part + (size_t)PT_SIDE * A.NP + m.pi;
     BMPC_UNROLL
@@ -1051,7 +1066,8 @@ BMPC_KBODY void k_points_body(const PipeArgs& A, int wave, int lane, LDSD* lds_p
 // k_curv: second-order kinematic terms of the Lagrangian Hessian (record fields F_CQQ, F_CQD) for the
 // instances in hess_mode (the list k_points built: wavefronts made of such instances only); forces from k_eval.
 // ------------------------------------------------------------------------------------------
-BMPC_KBODY void k_curv_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
+template <class AT>
+BMPC_KBODY void k_curv_body(const AT& A, int wave, int lane, LDSD* lds) {
     const int count = A.L.cnt[10], N = A.N;
     if (A.o.hess != 2 || wave * ipw_of(N) >= count) return;
     PairMap m = pair_map(A, A.L.curv, count, wave, lane);
@@ -1060,7 +1076,7 @@ BMPC_KBODY void k_curv_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
     E.init(lds, A.hrec, lane, hrec_of(A, m.b, m.k), m.valid, F_CQP);
     BMPC_SYNC();
     double zeta[NZ], y[NZ];
-    load_zeta(cur_zeta(A, A.st[m.b].flip), A.NP, m.pi, zeta);
+    load_zeta(A, cur_zeta(A, A.st[m.b].flip), m.pi, zeta);
     nat_all(zeta, dc, y);
     KinT K;
     double Jl[3][7];
@@ -1107,7 +1123,8 @@ BMPC_KBODY void k_curv_body(const PipeArgs& A, int wave, int lane, LDSD* lds) {
 
 // line-search start of one instance (fraction-to-boundary step lengths, merit derivative) from the per-pair partials of
 // k_step, summed in pair order (fixed order -> reproducible)
-BMPC_INL void ls0_instance(const PipeArgs& A, int b) {
+template <class AT>
+BMPC_INL void ls0_instance(const AT& A, int b) {
     const int N = A.N;
     GST st = A.st + b;
     GCD P = A.part + pair_of(A, b, 1);
@@ -1175,7 +1192,8 @@ BMPC_INL bool ls_decide(const PipeArgs& A, int b, double f1, double th1, double 
     }
     return false;
 }
-BMPC_INL bool ls_instance(const PipeArgs& A, int b, bool requeue) {      // the trial point's pieces from the per-pair partials, in pair order
+template <class AT>
+BMPC_INL bool ls_instance(const AT& A, int b, bool requeue) {      // the trial point's pieces from the per-pair partials, in pair order
     GCD P = A.part + pair_of(A, b, 1);
     double f1 = 0, th1 = 0, ls1 = 0;
     for (int k = 0; k < A.N - 1; k++) { f1 += P[PT_F1 * A.NP + k]; th1 += P[PT_TH1 * A.NP + k]; ls1 += P[PT_LS1 * A.NP + k]; }
@@ -1185,8 +1203,8 @@ BMPC_INL bool ls_instance(const PipeArgs& A, int b, bool requeue) {      // the 
 // ------------------------------------------------------------------------------------------
 // k_step: row steps for the Newton direction dz
 // ------------------------------------------------------------------------------------------
-struct StepVisitor {
-    const PipeArgs* A; size_t pi; bool valid;
+template <class AT> struct StepVisitorT {
+    const AT* A; size_t pi; bool valid;
     double mu, tau;
     const double* dy;     // natural step
     const double* dzt;    // zeta step
@@ -1197,10 +1215,11 @@ struct StepVisitor {
                                                       // instead of one per row), -mu sum dt/t over the rows of this pair
     template <int S0, int CNT> BMPC_INL void group(unsigned act) {      // bit i of act: slot S0 + i may be a constraint row (else: not loaded)
         static_assert(CNT <= ROW_GROUP_MAX, "row group size");
+        GCD tb = soa_col(*A, tc, pi), zb = soa_col(*A, zc, pi);
         BMPC_UNROLL
         for (int i = 0; i < CNT; i++) {
-            size_t o = (size_t)(S0 + i) * A->NP + pi;
-            if ((act >> i) & 1u) { gt[i] = tc[o]; gz[i] = zc[o]; } else { gt[i] = 1.0; gz[i] = 0.0; }
+            size_t o = soa_off(*A, (size_t)(S0 + i) * A->NP, pi);
+            if ((act >> i) & 1u) { gt[i] = tb[o]; gz[i] = zb[o]; } else { gt[i] = 1.0; gz[i] = 0.0; }
         }
     }
     BMPC_INL void fin(int s, double h, double adot) {
@@ -1209,7 +1228,7 @@ struct StepVisitor {
         // part of the merit derivative
         const double c = -h - adot, t = gt[s - row_group_base(s)], z = gz[s - row_group_base(s)];
         const double rt = BMPC_RCP(t), dti = c - t, dzi = (mu - z * c) * rt;
-        if (valid) { size_t o = (size_t)s * A->NP + pi; A->dt[o] = c; }
+        if (valid) { size_t o = soa_off(*A, (size_t)s * A->NP, pi); soa_col(*A, A->dt, pi)[o] = c; }
         rp = fmax(rp, -dti * rt);
         if (-dzi * rdd > rdn * z) { rdn = -dzi; rdd = z; }          // -dzi / z > rdn / rdd  (z, rdd > 0)
         dbar -= mu * dti * rt;
@@ -1232,6 +1251,7 @@ struct StepVisitor {
     }
     template <int C> BMPC_INL void point_end() {}
 };
+typedef StepVisitorT<PipeArgs> StepVisitor;
 
 template <int C>
 BMPC_INL void point_dirs(const KinT& K, const double* dyq, double dpt[6][3]) {
@@ -1250,7 +1270,8 @@ BMPC_INL void point_dirs(const KinT& K, const double* dyq, double dpt[6][3]) {
     }
 }
 
-BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par) {
+template <class AT>
+BMPC_KBODY void k_step_body(const AT& A, int wave, int lane, LDSD* lds_par) {
     const int count = A.L.cnt[1], N = A.N;
     if (wave * ipw_of(N) >= count) return;
     PairMap m = pair_map(A, A.L.step, count, wave, lane);
@@ -1274,15 +1295,15 @@ BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
     // of the next phase is computed early.  Row order is that of the single walk -- box, pose, phi and terminal, points -- and no
     // expression changes, so rp, rdn / rdd and dbar are bitwise what the single walk gave.
     // ---- 1: the box and non-negativity rows need the natural coordinates and the two steps only ----
-    load_zeta(cur_zeta(A, flip), A.NP, m.pi, S.zeta);
+    load_zeta(A, cur_zeta(A, flip), m.pi, S.zeta);
     double dzt[NZ], dy[NZ];
-    load_zeta(A.dz, A.NP, m.pi, dzt);
+    load_zeta(A, A.dz, m.pi, dzt);
     nat_all(S.zeta, dc, S.y);
     nat_all(dzt, dc, dy);
-    StepVisitor V;
+    StepVisitorT<AT> V;
     V.A = &A; V.pi = m.pi; V.valid = m.valid; V.mu = mu; V.tau = fmax(0.99, 1.0 - mu); V.tc = cur_t(A, flip); V.zc = cur_z(A, flip);
     V.dy = dy; V.dzt = dzt; V.rp = 0.0; V.rdn = 0.0; V.rdd = 1.0; V.dbar = 0.0;
-    walk_rows<StepVisitor, WR_BOX>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    walk_rows<StepVisitorT<AT>, WR_BOX>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
     BMPC_PIN(V.rp); BMPC_PIN(V.rdn); BMPC_PIN(V.rdd); BMPC_PIN(V.dbar);
     BMPC_UNROLL
     for (int j = 0; j < 7; j++) BMPC_PIN(S.y[Z_Q + j]);
@@ -1339,10 +1360,10 @@ BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
             double gg = 2 * wts[10] * S.y[Z_D + i] + (i != 4 ? 2 * wts[8] * (pg[P_SLACKS0 + i] + S.y[Z_D + i]) : 0.0);
             dphi_f += gg * dy[Z_D + i];
         }
-    walk_rows<StepVisitor, WR_POSE>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    walk_rows<StepVisitorT<AT>, WR_POSE>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
     BMPC_PIN(V.rp); BMPC_PIN(V.rdn); BMPC_PIN(V.rdd); BMPC_PIN(V.dbar);
     // ---- 4: the collision-point rows need the point positions, their directions and the d slacks only ----
-    walk_rows<StepVisitor, WR_PT0 | WR_PT1>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    walk_rows<StepVisitorT<AT>, WR_PT0 | WR_PT1>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
     if (m.valid) {
         GD P = A.part + m.pi;
         P[PT_DPHIF * A.NP] = dphi_f;
@@ -1357,8 +1378,8 @@ BMPC_KBODY void k_step_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
 // ------------------------------------------------------------------------------------------
 // k_trial: zeta + alpha dz, t + alpha dt -> f, theta, sum log t
 // ------------------------------------------------------------------------------------------
-struct TrialVisitor {
-    const PipeArgs* A; size_t pi; bool valid;
+template <class AT> struct TrialVisitorT {
+    const AT* A; size_t pi; bool valid;
     double alpha;
     GCD tc; GD tn_out;                                // cur_t (read) and oth_t (the trial slacks go there) of the instance
     // the multipliers' step does not depend on the primal step length: the first trial of an iteration also writes
@@ -1373,17 +1394,19 @@ struct TrialVisitor {
         static_assert(CNT <= ROW_GROUP_MAX, "row group size");
         // (z is loaded with t and c, one memory round trip per group, also by the later trials of a search, which do not use it)
         double gz[CNT];
+        GCD tb = soa_col(*A, tc, pi), cb = soa_col(*A, A->dt, pi), zb = soa_col(*A, zc, pi);
         BMPC_UNROLL
         for (int i = 0; i < CNT; i++) {
-            size_t o = (size_t)(S0 + i) * A->NP + pi;
-            if ((act >> i) & 1u) { gt[i] = tc[o]; gc[i] = A->dt[o]; gz[i] = zc[o]; } else { gt[i] = 1.0; gc[i] = 1.0; gz[i] = 0.0; }
+            size_t o = soa_off(*A, (size_t)(S0 + i) * A->NP, pi);
+            if ((act >> i) & 1u) { gt[i] = tb[o]; gc[i] = cb[o]; gz[i] = zb[o]; } else { gt[i] = 1.0; gc[i] = 1.0; gz[i] = 0.0; }
         }
         if (dual) {
             // a slot is live iff z > 0 (inactive slots keep t = 1, z = 0 in both copies from k_init); done here, on the whole
             // group at once, so that no multiplier stays in a register while the group's rows are walked
+            GD zo = soa_col(*A, zn_out, pi);
             BMPC_UNROLL
             for (int i = 0; i < CNT; i++)
-                if (gz[i] > 0.0) zn_out[(size_t)(S0 + i) * A->NP + pi] = gz[i] + ad * ((mu - gz[i] * gc[i]) * BMPC_RCP(gt[i]));
+                if (gz[i] > 0.0) zo[soa_off(*A, (size_t)(S0 + i) * A->NP, pi)] = gz[i] + ad * ((mu - gz[i] * gc[i]) * BMPC_RCP(gt[i]));
         }
     }
     BMPC_INL void fin(int s, double h) {
@@ -1394,7 +1417,7 @@ struct TrialVisitor {
         thr += fabs(h + tn);
         int e;
         lp = frexp(lp * tn, &e); le += e;
-        if (valid) tn_out[(size_t)s * A->NP + pi] = tn;
+        if (valid) soa_col(*A, tn_out, pi)[soa_off(*A, (size_t)s * A->NP, pi)] = tn;
     }
     BMPC_INL void skip(int) {}
     BMPC_INL void diag(int s, int, double, double h) { fin(s, h); }
@@ -1404,14 +1427,15 @@ struct TrialVisitor {
     template <int C> BMPC_INL void point(int s, const double*, double h) { fin(s, h); }
     template <int C> BMPC_INL void point_end() {}
 };
+typedef TrialVisitorT<PipeArgs> TrialVisitor;
 
 // One part (ROLES: stage.hpp WR_*) of the trial point of pair (b, k): trial slacks, multiplier update, the part's share of theta and of
 // sum log t; WR_POSE also writes the trial zeta and adds the dynamics defect and the objective.
 struct TrialPart { double f, th, thr, lp; int le; };
 // t_out / zeta_out: where the trial slacks and the trial zeta go, indexed like the workspace arrays (field * A.NP + pi); null = the other
 // copy of the double-buffered arrays
-template <int ROLES>
-BMPC_INL void trial_part(const PipeArgs& A, PGP pg, int b, int k, size_t pi, bool live, bool dual, double alpha, int flip, TrialPart& R,
+template <int ROLES, class AT>
+BMPC_INL void trial_part(const AT& A, PGP pg, int b, int k, size_t pi, bool live, bool dual, double alpha, int flip, TrialPart& R,
                          GD t_out = nullptr, GD zeta_out = nullptr) {
     const int N = A.N, n_w = 44 * N + 6;
     const bool term = (k == N - 1);
@@ -1429,13 +1453,13 @@ BMPC_INL void trial_part(const PipeArgs& A, PGP pg, int b, int k, size_t pi, boo
             for (int i = 0; i < NZ; i++) zo[(size_t)i * A.NP + pi] = S.zeta[i];
     }
     nat_all(S.zeta, dc, S.y);
-    TrialVisitor V;
+    TrialVisitorT<AT> V;
     V.A = &A; V.pi = pi; V.valid = live; V.alpha = alpha; V.thr = 0.0; V.lp = 1.0; V.le = 0; V.tc = cur_t(A, flip); V.tn_out = t_out ? t_out : oth_t(A, flip);
     V.dual = dual; V.ad = A.st[b].ad; V.mu = A.st[b].mu; V.zc = cur_z(A, flip); V.zn_out = oth_z(A, flip);
     // The walk in three phases, each with its own inputs: the box rows need the natural coordinates only and run BEFORE kinematics
     // and reference context exist; the pose rows need the context; the collision points need the joint origins only.  (One walk
     // over everything kept coordinates, context and kinematics alive through all row groups: the kernel's spills.)
-    if constexpr ((ROLES & WR_BOX) != 0) walk_rows<TrialVisitor, WR_BOX>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    if constexpr ((ROLES & WR_BOX) != 0) walk_rows<TrialVisitorT<AT>, WR_BOX>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
     BMPC_SCHED_FENCE();
     if constexpr ((ROLES & (WR_POSE | WR_PT0 | WR_PT1)) != 0) kin_chain(A.rc, S.y + Z_Q, S.K);
     R.th = 0.0; R.f = 0.0;
@@ -1465,11 +1489,11 @@ BMPC_INL void trial_part(const PipeArgs& A, PGP pg, int b, int k, size_t pi, boo
         BMPC_UNROLL
         for (int a = 0; a < 3; a++) { S.C.pose[a] = S.K.pee[a]; S.C.pose[3 + a] = S.y[Z_PI + a] + 0.5 * dc.dt * S.C.v[3 + a]; }
         seg_ctx_eval(pg, A.N, k, S.y, iw0, S.C);          // (= stage_point)
-        walk_rows<TrialVisitor, WR_POSE>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+        walk_rows<TrialVisitorT<AT>, WR_POSE>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
         R.th = th; R.f = S.C.fv;
     }
     BMPC_SCHED_FENCE();
-    if constexpr ((ROLES & (WR_PT0 | WR_PT1)) != 0) walk_rows<TrialVisitor, ROLES & (WR_PT0 | WR_PT1)>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
+    if constexpr ((ROLES & (WR_PT0 | WR_PT1)) != 0) walk_rows<TrialVisitorT<AT>, ROLES & (WR_PT0 | WR_PT1)>(pg, lbx, ubx, N, k, S.y, S.zeta, S.K, S.C, V);
     R.thr = V.thr; R.lp = V.lp; R.le = V.le;
 }
 
@@ -1478,8 +1502,8 @@ BMPC_INL void trial_part(const PipeArgs& A, PGP pg, int b, int k, size_t pi, boo
 // wavefront holds the natural coordinates, the reference context AND the point positions: the parts fit half the register file (two
 // workgroups per CU instead of one wavefront per SIMD that spills), and a pair's dependent memory round trips -- one per row group --
 // run side by side in the four wavefronts instead of one after the other.  tid = thread index in the workgroup.
-template <int NW>
-BMPC_KBODY void k_trial_body_t(const PipeArgs& A, int wave, int tid, LDSD* lds_par) {
+template <int NW, class AT>
+BMPC_KBODY void k_trial_body_t(const AT& A, int wave, int tid, LDSD* lds_par) {
     static_assert(NW == 1 || NW == 4, "parts of the trial walk");
     const int count = A.L.cnt[2], N = A.N;
     if (wave * ipw_of(N) >= count) return;
@@ -1559,7 +1583,8 @@ BMPC_KBODY void k_trial_body(const PipeArgs& A, int wave, int lane, LDSD* lds_pa
 constexpr int TRIAL_SPEC = 4;
 static_assert(TRIAL_SPEC - 1 <= RIC_NATT - 1 && NSLOT + NZ <= KREC, "candidate trial points fit the speculative gain copies");
 static_assert(TRIAL_SPEC * 64 * 3 + IPW_MAX <= TRIAL_SPEC * 64 * TRIAL_COMB, "k_trial_spec's LDS fits trial_lds_doubles(N, 4)");
-BMPC_KBODY void k_trial_spec_body(const PipeArgs& A, int wave, int tid, LDSD* lds_par) {
+template <class AT>
+BMPC_KBODY void k_trial_spec_body(const AT& A, int wave, int tid, LDSD* lds_par) {
     const int count = A.L.cnt[2], N = A.N;
     if (wave * ipw_of(N) >= count) return;
     const int lane = tid & 63, role = tid >> 6;
@@ -1669,7 +1694,7 @@ BMPC_KBODY void k_out_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par)
     for (int c = 0; c < 3; c++) iw0[c] = lbx[28 * N + (3 + c) * N];
     StagePoint S;
     GCD zc = cur_zeta(A, A.st[m.b].flip);
-    load_zeta(zc, A.NP, pi, S.zeta);           // the iterate the instance finished on
+    load_zeta(A, zc, pi, S.zeta);           // the iterate the instance finished on
     stage_point(A, pg, iw0, k, dc, S);
     GD x = A.x + b * n_w;
     BMPC_UNROLL
@@ -1826,7 +1851,7 @@ BMPC_KBODY void k_mult_body(const PipeArgs& A, int wave, int lane, LDSD* lds_par
     BMPC_UNROLL
     for (int c = 0; c < 3; c++) iw0[c] = lbx[28 * N + (3 + c) * N];
     StagePoint S;
-    load_zeta(cur_zeta(A, A.st[m.b].flip), A.NP, pi, S.zeta);     // the final point of the instance
+    load_zeta(A, cur_zeta(A, A.st[m.b].flip), pi, S.zeta);     // the final point of the instance
     stage_point(A, pg, iw0, k, dc, S);
     double G[6][7], g12[12];
     kin_G(S.K, S.Jl, S.y + Z_DQ, G);

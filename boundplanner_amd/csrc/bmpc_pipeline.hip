@@ -2,6 +2,7 @@
 // Device code: bmpc_stage.hpp / bmpc_pair_kernels.hpp / bmpc_ric_kernel.hpp.  Host sequencing:
 // bmpc_capi.hip (pipe_solve).
 #include "bmpc_platform_hip.hpp"
+#include <atomic>
 #include <cstdlib>
 #include <utility>
 
@@ -163,22 +164,47 @@ extern "C" hipError_t bmpc_pipe_launch_retire_admit(const PipeArgsH* A, int n_ma
     return hipGetLastError();
 }
 
+// The pair kernels compiled for the workspace's horizon (bmpc_pair_fixed.hpp: the SoA strides are compile-time constants), or null:
+// the generic kernels of this file.  Slot-major layout (NP = N - 1) and N = 20 or 30 only.  BMPC_FIXED_STRIDE=0 in the environment
+// (read once): the generic kernels everywhere -- A/B runs and the test that the two agree bitwise.
+static bmpc_pair_launcher fixed_launcher(const PipeArgsH* A) {
+    static const int fixed_stride = env_int("BMPC_FIXED_STRIDE", 1);
+    if (!fixed_stride || A->NP != (size_t)(A->N - 1)) return nullptr;
+    return A->N == 20 ? bmpc_pair_launch_n20 : A->N == 30 ? bmpc_pair_launch_n30 : nullptr;
+}
+static std::atomic<long> fixed_launches{0};      // launches that went to a fixed-horizon kernel (the tests' proof of which kernels ran)
+extern "C" long bmpc_pipe_fixed_launches(void) { return fixed_launches.load(); }
+#define LAUNCH_FX(fx, kern, nb, nt, lds_doubles) \
+    (fixed_launches++, fx(kern, A, nw, (unsigned)(nb), (unsigned)(nt), (lds_doubles) * sizeof(double), st))
+
 // the evaluation launches of a super-step for nw groups of pairs: k_points || k_pose, then k_eval (|| k_curv)
 static void launch_eval(const PipeArgsH* A, int nw, hipStream_t st) {
     static const int split_launches = env_int("BMPC_SPLIT_LAUNCHES", 0);
     static const int eval_split_wgs = env_int("BMPC_EVAL_SPLIT_WGS", BMPC_EVAL_SPLIT_WGS);      // (read once; 0 = never)
+    const bmpc_pair_launcher fx = fixed_launcher(A);
     if (split_launches) {
-        LAUNCH_DYN(bmpc_k_points, nw, 64, pair_lds_doubles(A->N, false));
-        LAUNCH_DYN(bmpc_k_pose, nw, 64, pair_lds_doubles(A->N, false));
-        if (nw <= eval_split_wgs) {
+        if (fx) {
+            LAUNCH_FX(fx, FX_POINTS, nw, 64, pair_lds_doubles(A->N, false));
+            LAUNCH_FX(fx, FX_POSE, nw, 64, pair_lds_doubles(A->N, false));
+        } else {
+            LAUNCH_DYN(bmpc_k_points, nw, 64, pair_lds_doubles(A->N, false));
+            LAUNCH_DYN(bmpc_k_pose, nw, 64, pair_lds_doubles(A->N, false));
+        }
+        if (nw <= eval_split_wgs && fx) {
+            LAUNCH_FX(fx, FX_EVAL_MAIN, nw, 64, pair_lds_doubles(A->N, true));
+            LAUNCH_FX(fx, FX_EVAL_CHAIN, nw, 64, pair_lds_doubles(A->N, true));
+        } else if (nw <= eval_split_wgs) {
             LAUNCH_DYN(bmpc_k_eval_main, nw, 64, pair_lds_doubles(A->N, true));
             LAUNCH_DYN(bmpc_k_eval_chain, nw, 64, pair_lds_doubles(A->N, true));
         } else
             LAUNCH_DYN(bmpc_k_eval, nw, 64, pair_lds_doubles(A->N, true));
         LAUNCH(bmpc_k_curv, nw, 64);
     } else if (nw > 0) {
-        hipLaunchKernelGGL(bmpc_k_points_pose, dim3(2 * nw), dim3(64), pair_lds_doubles(A->N, false) * sizeof(double), st, *A, nw);
-        if (nw <= eval_split_wgs)
+        if (fx) LAUNCH_FX(fx, FX_POINTS_POSE, 2 * nw, 64, pair_lds_doubles(A->N, false));
+        else hipLaunchKernelGGL(bmpc_k_points_pose, dim3(2 * nw), dim3(64), pair_lds_doubles(A->N, false) * sizeof(double), st, *A, nw);
+        if (nw <= eval_split_wgs && fx)
+            LAUNCH_FX(fx, FX_EVAL_CURV_SPLIT, A->o.hess == 2 ? 3 * nw : 2 * nw, 64, pair_lds_doubles(A->N, true));
+        else if (nw <= eval_split_wgs)
             hipLaunchKernelGGL(bmpc_k_eval_curv_split, dim3(A->o.hess == 2 ? 3 * nw : 2 * nw), dim3(64), pair_lds_doubles(A->N, true) * sizeof(double), st, *A, nw);
         else
             hipLaunchKernelGGL(bmpc_k_eval_curv, dim3(A->o.hess == 2 ? 2 * nw : nw), dim3(64), pair_lds_doubles(A->N, true) * sizeof(double), st, *A, nw);
@@ -207,14 +233,20 @@ static void launch_direction(PipeArgsH* A, int n_act, int nw, hipStream_t st, hi
     if (e1) (void)hipEventRecord(e1, st);
     if (was_lat) *was_lat = n_act < lat_below || n_act < spec_below;      // (the launches of the tail regime, whichever kernels ran)
     LAUNCH(bmpc_k_fwd, n_act, 64);
-    LAUNCH_DYN(bmpc_k_step, nw, 64, pair_lds_doubles(A->N, false));
+    if (const bmpc_pair_launcher fx = fixed_launcher(A)) LAUNCH_FX(fx, FX_STEP, nw, 64, pair_lds_doubles(A->N, false));
+    else LAUNCH_DYN(bmpc_k_step, nw, 64, pair_lds_doubles(A->N, false));
 }
 
 // the line search of a super-step for nw groups of pairs: trial points (+ multiplier update) + filter test, backtracking inside
 static void launch_trial(const PipeArgsH* A, int nw, hipStream_t st) {
     // BMPC_TRIAL_SPEC_WGS (read once; 0 = never): up to that many groups of pairs the step lengths of a line search are tried side by side (slot-major layout)
     static const int trial_spec_wgs = env_int("BMPC_TRIAL_SPEC_WGS", BMPC_TRIAL_SPEC_WGS);
-    if (nw <= trial_spec_wgs && A->NP == (size_t)(A->N - 1)) LAUNCH_DYN(bmpc_k_trial_spec, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
+    const bmpc_pair_launcher fx = fixed_launcher(A);
+    if (nw <= trial_spec_wgs && A->NP == (size_t)(A->N - 1)) {
+        if (fx) LAUNCH_FX(fx, FX_TRIAL_SPEC, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
+        else LAUNCH_DYN(bmpc_k_trial_spec, nw, 64 * TRIAL_SPEC, trial_lds_doubles(A->N, TRIAL_SPEC));
+    } else if (fx && BMPC_TRIAL_NW == 1)      // (the four-wavefront k_trial of an experiment build has no fixed-horizon form)
+        LAUNCH_FX(fx, FX_TRIAL, nw, 64, trial_lds_doubles(A->N, 1));
     else
         LAUNCH_DYN(bmpc_k_trial, nw, 64 * BMPC_TRIAL_NW, trial_lds_doubles(A->N, BMPC_TRIAL_NW));
 }

@@ -151,6 +151,22 @@ typedef PipeArgsT<1> PipeArgs;           // device view (same layout)
 static_assert(sizeof(PipeArgsH) == sizeof(PipeArgs), "host/device argument layouts differ");
 typedef BMPC_AS1 InstState* GST;
 
+template <int NF> struct PipeArgsN;      // (below, after pipe_slot_block)
+template <class AT> struct FixedView { static constexpr bool value = false; };
+template <int NF> struct FixedView<PipeArgsN<NF>> { static constexpr bool value = true; };
+// Element `off` (= field * A.NP, + 1 for the next stage) of the lane's column pi of an SoA array is  soa_col(A, arr, pi)[soa_off(A, off, pi)].
+// Fixed view: the lane's base pointer arr + pi, formed once per array (and outside the tests of a row's activity), then the constant --
+// one base register per array and an immediate per access.  Generic view: arr[off + pi], the sum as it always was (the strides are in
+// scalar registers; the generic kernels compile as before).
+template <class AT, class P> BMPC_INL P soa_col(const AT&, P arr, size_t pi) {
+    if constexpr (FixedView<AT>::value) return arr + pi;
+    else return arr;
+}
+template <class AT> BMPC_INL size_t soa_off(const AT&, size_t off, size_t pi) {
+    if constexpr (FixedView<AT>::value) return off;
+    else return off + pi;
+}
+
 // The iterate's slacks, row multipliers and zeta live in t / z / zeta or in t_t / z_t / zeta_t, per instance (InstState.flip):
 // k_trial writes the trial point (and the updated multipliers, which do not depend on the primal step length) into the other
 // copy and an accepted trial becomes the iterate by flipping the bit -- no copy pass, no update pass.
@@ -166,7 +182,18 @@ template <class AT> BMPC_INL size_t krec_of(const AT& A, int b, int k) { return 
 
 // workspace of `cap` slots: size in doubles, and the array bases inside it
 constexpr size_t PIPE_SOA_FIELDS = 3 * (size_t)NZ + 5 * (size_t)NSLOT + NPART;
-inline size_t pipe_slot_block(int N) { return ((PIPE_SOA_FIELDS + HREC + KREC) * (size_t)(N - 1) + 15) / 16 * 16 + 16; }
+constexpr size_t pipe_slot_block(int N) { return ((PIPE_SOA_FIELDS + HREC + KREC) * (size_t)(N - 1) + 15) / 16 * 16 + 16; }
+// The device view with the horizon fixed at compile time, for the thread-per-pair kernels in the slot-major layout (NP = N - 1).
+// N and NP hide the members of the argument block: a body that takes its view as `const AT& A` reads A.N, A.NP as constants, every
+// row stride (field * A.NP) folds into the instruction's offset, and N - 1, ipw_of(N), the k == N - 1 tests follow; so are the slot
+// strides SS = HS = KS (pipe_carve).  Nothing is
+// added to the block: a launch argument is read through either view (bmpc_pipeline.hip, DVN).  Integer address arithmetic only.
+template <int NF> struct PipeArgsN : PipeArgs {
+    static_assert(NF >= 3, "horizon");
+    static constexpr int N = NF;
+    static constexpr size_t NP = (size_t)(NF - 1);
+    static constexpr size_t SS = pipe_slot_block(NF), HS = SS, KS = SS;
+};
 inline size_t pipe_np_field_major(int cap, int N) { return ((size_t)cap * (N - 1) + 63) / 64 * 64 + 64; }
 inline size_t pipe_workspace_doubles(int cap, int N, int slot_major) {
     return (slot_major ? pipe_slot_block(N) * (size_t)cap + 64
@@ -198,7 +225,7 @@ BMPC_HD int ipw_of(int N) { int i = 64 / (N - 1); return i < IPW_MAX ? i : IPW_M
 
 // lanes -> pairs inside a wave: ipw_of(N) instances per wave, lane = li*(N-1) + (k-1)
 struct PairMap { int b, k, li; bool valid; size_t pi; };
-BMPC_INL PairMap pair_map(const PipeArgs& A, GCI list, int count, int wave, int lane) {
+template <class AT> BMPC_INL PairMap pair_map(const AT& A, GCI list, int count, int wave, int lane) {
     const int S = A.N - 1, ipw = ipw_of(A.N);
     int li = lane / S, kk = lane - li * S;
     int e = wave * ipw + li;
@@ -236,8 +263,8 @@ BMPC_INL void stage_masks(LDSD* lds_par, int ipw, int wave, int lane, int count)
     BMPC_SYNC();
 }
 // NTHR: threads of the workgroup (all of them must call it; `lane` = thread index in the workgroup)
-template <bool BATCHED = true, int NTHR = 64>
-BMPC_INL PGP stage_params(const PipeArgs& A, GCI list, int count, int wave, int lane, const PairMap& m, LDSD* lds_par) {
+template <bool BATCHED = true, int NTHR = 64, class AT>
+BMPC_INL PGP stage_params(const AT& A, GCI list, int count, int wave, int lane, const PairMap& m, LDSD* lds_par) {
     const int ipw = ipw_of(A.N);
     if constexpr (!BATCHED) {
         for (int li = 0; li < ipw; li++) {

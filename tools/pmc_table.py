@@ -1,13 +1,13 @@
 """Per-kernel table of DESIGN.md section 3.2 from a profile round (tools/profile_round.sh): GPU busy time, wait share, HBM bytes,
 FP64 issued, LDS conflict share -- from pmc_summary.csv, pmc_traffic.json and kernel_stats_depth1_merge1.csv."""
-import collections, csv, json, sys
+import collections, csv, json, sys, re
 d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/prof_round"
 acc = collections.defaultdict(dict)
 for r in list(csv.reader(open(f"{d}/pmc_summary.csv")))[1:]:
     acc[r[0]][r[1]] = float(r[2])
 tr = json.load(open(f"{d}/pmc_traffic.json"))
 NB = 3          # batches in the depth-1 stats run of tools/profile_round.sh (--steps 2 --warmup 1)
-ks = {r[0].split("(")[0]: float(r[2]) / 1e6 / NB for r in list(csv.reader(open(f"{d}/kernel_stats_depth1_merge1.csv")))[1:]}
+ks = {re.sub(r"_n\d+$", "", r[0].split("(")[0]): float(r[2]) / 1e6 / NB for r in list(csv.reader(open(f"{d}/kernel_stats_depth1_merge1.csv")))[1:]}
 tot_flop = 0
 print("kernel            busy_ms  trace_ms  wait  HBM_GB  GFLOP  lds_conf")
 for k in ("bmpc_k_ric", "bmpc_k_ric_att_thr", "bmpc_k_eval_main", "bmpc_k_eval_chain", "bmpc_k_eval", "bmpc_k_pose", "bmpc_k_step", "bmpc_k_trial", "bmpc_k_trial_spec", "bmpc_k_points", "bmpc_k_curv", "bmpc_k_fwd"):

@@ -3,7 +3,7 @@ interior-point iterations (max_iter 4: every instance is alive in every super-st
 `rocprofv3 --kernel-trace`, then `python tools/scaling_trace.py --parse <kernel_trace.csv>` prints, per B, the mean duration
 of each pipeline kernel in the FIRST super-step of that solve (all B instances alive; later launches of the same solve work on
 fewer and fewer instances).  One wavefront per SIMD = 1024 wavefronts = 3072 instances at N=20."""
-import argparse
+import argparse, re
 import collections
 import csv
 import os
@@ -34,7 +34,7 @@ def parse(path):
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     solves, cur = [], []
     for r in rows:
-        name = r["Kernel_Name"].split("(")[0]
+        name = re.sub(r"_n\d+$", "", r["Kernel_Name"].split("(")[0])      # (bmpc_k_step_n20: the kernel compiled for N = 20, same column)
         if name == "bmpc_k_eval_curv_split": name = "bmpc_k_eval_curv"      # (the two-wavefront k_eval beside k_curv: same column)
         if name == "bmpc_k_trial_spec": name = "bmpc_k_trial"
         if name == "bmpc_k_init_inst" and cur:

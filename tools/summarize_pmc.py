@@ -1,11 +1,11 @@
 """Summarise rocprofv3 --pmc CSVs per kernel of the pipeline (helper for profiles/, not a test):
 sum of every counter over all launches of each kernel, number of dispatches."""
-import collections, csv, glob, sys
+import collections, csv, glob, sys, re
 acc = collections.defaultdict(float); calls = collections.defaultdict(set)
 for d in [a for a in sys.argv[1:] if not a.startswith('--') and not a.endswith('.json')]:
     for f in glob.glob(f"{d}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            k = r["Kernel_Name"].split("(")[0]
+            k = re.sub(r"_n\d+$", "", r["Kernel_Name"].split("(")[0])      # (bmpc_k_step_n20: the kernel compiled for N = 20)
             if k.startswith("bmpc_"):
                 acc[(k, r["Counter_Name"])] += float(r["Counter_Value"]); calls[(k, r["Counter_Name"])].add(r["Dispatch_Id"])
 print("kernel,counter,sum,dispatches")

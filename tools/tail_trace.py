@@ -1,11 +1,11 @@
 """Summarise a rocprofv3 --kernel-trace CSV of ONE synchronous batch: per super-step (k_points ... k_rotate) the kernel
 durations and the gaps between kernels, separately for the bulk and the straggler tail (helper for profiles/)."""
-import csv, sys, collections
+import csv, sys, collections, re
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if r["Kernel_Name"].startswith("bmpc_k_")]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 steps, cur = [], []
 for r in rows:
-    name = r["Kernel_Name"].split("(")[0]
+    name = re.sub(r"_n\d+$", "", r["Kernel_Name"].split("(")[0])      # (bmpc_k_step_n20: the kernel compiled for N = 20)
     if name in ("bmpc_k_init_inst", "bmpc_k_init", "bmpc_k_init_fin", "bmpc_k_out", "bmpc_k_fin", "bmpc_k_mult", "bmpc_k_mult_sweep"):
         continue
     cur.append((name, int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
