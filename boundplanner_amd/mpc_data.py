@@ -32,7 +32,12 @@ def _list(rows):
 def mpc_data(traj_data, ref_data, err_data, mpc, aux=None, t_comp=0.0, t_loop=0.0, t_overhead=0.0, cost=0.0, iterations=0, fails=()):
     """One MPCData record (dict keyed by the message's field names; `Vector[]` fields are lists of 1-D arrays, one per
     horizon stage; `Vector` fields 1-D arrays).  `mpc`: the BoundMPC object after the step; `aux`: the dict returned by
-    BoundMPC.prepare (sets, bases) when available."""
+    BoundMPC.prepare (collision sets) when available.
+
+    The reference declares the four end-effector set fields and fills none of them, so the convention is this package's, one for
+    both decoders: `a_set` / `b_set` are the set of the segment stage 1 lies in, `a_set_next` / `b_set_next` the set of the
+    next-segment selector of the step (1, 2 or 3: the first split index still at N before the step) -- the `a_current` / `a_next`
+    that BoundMPC.compute_return_data stores in ref_data at stage 1, and what from_device_record reads from the device record."""
     rp = mpc.ref_path
     d = {k: [] for k in FIELDS}
     d.update(t_comp=float(t_comp), t_loop=float(t_loop), t_overhead=float(t_overhead), phi_max=float(np.ravel(mpc.phi_max)[0]),
@@ -52,10 +57,11 @@ def mpc_data(traj_data, ref_data, err_data, mpc, aux=None, t_comp=0.0, t_loop=0.
         for name, c in _COL.items():
             d["a_set_" + name] = np.asarray(aj[c], float).ravel()
             d["b_set_" + name] = bj[c].copy()
-        a_set, b_set = np.asarray(aux["a_set"], float), np.asarray(aux["b_set"], float)
-        d["a_set"], d["b_set"] = a_set[0].ravel(), b_set[0].copy()
-        if a_set.shape[0] > 1:
-            d["a_set_next"], d["b_set_next"] = a_set[1].ravel(), b_set[1].copy()
+    # end-effector sets: what compute_return_data notes down at stage 1 (BoundMPC.py:805-809) -- current = the set of stage 1's
+    # segment, next = the set of the first segment without a split index (reference_function's a_next / b_next)
+    if "a_current" in ref_data:
+        d["a_set"], d["b_set"] = np.asarray(ref_data["a_current"], float).ravel(), np.asarray(ref_data["b_current"], float).copy()
+        d["a_set_next"], d["b_set_next"] = np.asarray(ref_data["a_next"], float).ravel(), np.asarray(ref_data["b_next"], float).copy()
     return d
 
 

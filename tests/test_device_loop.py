@@ -31,9 +31,11 @@ def test_so3_helpers_match_scipy():
         assert np.abs(e - R.from_matrix(M).as_euler("zyx")).max() < 1e-12
 
 
-def compare_record_with_host_mirror(rec, N, node, k, tol=1e-9):
+def compare_record_with_host_mirror(rec, N, node, k, tol=1e-9, set_tol=2e-6, need_sets=False):
     """The device loop's MPCData record of a step (decoded by mpc_data.from_device_record) against mpc_data.from_node of the host
-    mirror that took the same step: every field both sides produce."""
+    mirror that took the same step: every field both sides produce.  set_tol: the set fields (collision sets of a scene with
+    obstacles: closest pairs to ~1e-7; traces without obstacles pass 1e-9); need_sets: the four end-effector set fields must be
+    there on both sides (a field the host side leaves empty is otherwise not compared)."""
     from boundplanner_amd import mpc_data
     d, h = mpc_data.from_device_record(rec, N), mpc_data.from_node(node)
     assert d["iterations"] == h["iterations"] and d["sector"] is not None and abs(d["phi_max"] - h["phi_max"]) < tol, k
@@ -42,17 +44,45 @@ def compare_record_with_host_mirror(rec, N, node, k, tol=1e-9):
         worst = max(np.abs(np.ravel(a) - np.ravel(b)).max() for a, b in zip(d[key], h[key]))
         assert worst < tol, (k, key, worst)
     assert np.abs(d["phi"] - h["phi"]).max() < tol and np.abs(d["dphi"] - h["dphi"]).max() < tol, k
+    if need_sets:
+        for key in ("a_set", "b_set", "a_set_next", "b_set_next"):
+            assert np.size(h[key]) == np.size(d[key]) == (45 if key[0] == "a" else 15), (k, key)
     for key in ("a_set", "b_set", "a_set_next", "b_set_next", "a_set_j3", "b_set_j3", "a_set_j5", "a_set_j6", "a_set_j67", "a_set_elbow", "b_set_elbow"):
         if np.size(h[key]):
-            assert np.abs(np.ravel(d[key]) - np.ravel(h[key])).max() < 2e-6, (k, key)       # (collision sets: closest pairs to ~1e-7)
+            assert np.abs(np.ravel(d[key]) - np.ravel(h[key])).max() < set_tol, (k, key)
     assert set(mpc_data.FIELDS) <= set(d)
 
 
-@pytest.mark.parametrize("fixture", ["closed_loop.npz", "closed_loop_n15.npz", "closed_loop_fail.npz", "closed_loop_patch.npz",
-                                     "closed_loop_scene.npz"])
-def test_replay_of_the_reference_trace(golden_dir, fixture):
-    """(scenarios: see tests/test_closed_loop.py TRACES)"""
-    g = np.load(os.path.join(golden_dir, fixture))
+def via_lists(g):
+    """The via path of a trace as the fresh lists update_reference takes (ReferencePath appends to them)."""
+    return [[a.copy() for a in g["via_" + k]] for k in ("p_via", "r_via", "bp1", "br1", "e_r_bound", "a_sets", "b_sets")]
+
+
+# state field -> trace key of the carried floats; the second list only in traces that record the via-point lists
+STATE_KEYS = [("pr_ref", "pr_ref"), ("iw_ref", "iw_ref"), ("phi_current", "phi_current"), ("dphi_current", "dphi_current"),
+              ("phi_max", "phi_max"), ("slacks0", "slacks0"), ("rp_pd", "rp_pd"), ("rp_phi_switch", "rp_phi_switch"),
+              ("q", "out_q"), ("dq", "out_dq"), ("ddq", "out_ddq"), ("jerk", "out_jerk"), ("v", "out_v"),
+              ("qf", "out_qf"), ("p_lie", "out_p_lie")]
+PATH_KEYS = [("rp_p", "rp_p"), ("rp_phi", "rp_phi"), ("rp_phi_max", "rp_phi_max")]
+
+
+def compare_state_with_trace(V, g, k, worst, where=()):
+    """The carried state after step k (a state_view of one rollout) against the reference's: integers and flags exactly,
+    floats to 1e-9."""
+    assert [int(s) for s in V["split"]] == [int(s) for s in g["split_idxs"][k]], (k, where, V["split"], g["split_idxs"][k])
+    assert int(V["sw"][0]) == int(g["switch"][k]) and int(V["error_count"][0]) == int(g["error_count"][k]), (k, where)
+    assert int(V["rp_sector"][0]) == int(g["sector"][k]), (k, where)
+    if "num_sectors" in g.files:
+        assert int(V["rp_num_sectors"][0]) == int(g["num_sectors"][k]), (k, where)
+    for f, key in STATE_KEYS + (PATH_KEYS if "rp_p" in g.files else []):
+        d = np.abs(V[f] - np.asarray(g[key][k]).reshape(-1)).max()
+        worst[f] = max(worst.get(f, 0.0), d)
+        assert d < 1e-9, (k, where, f, d)
+
+
+def replay_trace(g, set_tol=2e-6, need_sets=False):
+    """A reference trace through the CPU build of the device loop: the solver arguments it prepares and the state it carries
+    against the trace, its MPCData record against the host mirror that takes the same steps.  -> worst deviation per field."""
     N = int(g["N"])
     base = get_default_params()
     params = Params(n=N, dt=base.dt, build=False, weights=base.weights, nr_segs=base.nr_segs)
@@ -74,10 +104,7 @@ def test_replay_of_the_reference_trace(golden_dir, fixture):
         if k == n_update:
             # new plan: host-side BoundMPC.update / ReferencePath construction, re-serialised; the carried
             # warm start, slacks0 and error count are NOT reset (a15) and stay what the device loop holds
-            shadow.update_reference([p.copy() for p in g["via_p_via"]], [r.copy() for r in g["via_r_via"]],
-                                    [b.copy() for b in g["via_bp1"]], [b.copy() for b in g["via_br1"]],
-                                    [e.copy() for e in g["via_e_r_bound"]], [a.copy() for a in g["via_a_sets"]],
-                                    [b.copy() for b in g["via_b_sets"]], [])
+            shadow.update_reference(*via_lists(g), [])
             keep = {f: state_view(lay, S)[f].copy() for f in ("slacks0", "error_count", "has_prev", "q", "dq", "ddq", "jerk", "v", "p_lie")}
             S = pack()
             for f, val in keep.items():
@@ -93,18 +120,17 @@ def test_replay_of_the_reference_trace(golden_dir, fixture):
             assert d < (2e-6 if (obs is not None and name == "p") else 1e-9), (k, name, d, np.argmax(np.abs(mine - big(g["call_" + name][k]))))
         _, rec = E.finish(N, params.dt, S, g["call_x"][k], prev, int(g["status"][k]), float(g["viol"][k]), int(g["iters"][k]), par=p)
         shadow.step()                                   # keeps the host mirror in lock step for the re-plan
-        compare_record_with_host_mirror(rec, N, shadow, k)      # the MPCData record the finish logic writes (boundmpcmsg/msg/MPCData.msg)
-        V = state_view(lay, S)
-        assert [int(s) for s in V["split"]] == list(g["split_idxs"][k]), k
-        assert int(V["sw"][0]) == int(g["switch"][k]) and int(V["error_count"][0]) == int(g["error_count"][k]), k
-        assert int(V["rp_sector"][0]) == int(g["sector"][k]), k
-        for f, key in (("pr_ref", "pr_ref"), ("iw_ref", "iw_ref"), ("phi_current", "phi_current"), ("dphi_current", "dphi_current"),
-                       ("phi_max", "phi_max"), ("slacks0", "slacks0"), ("rp_pd", "rp_pd"), ("rp_phi_switch", "rp_phi_switch"),
-                       ("q", "out_q"), ("dq", "out_dq"), ("ddq", "out_ddq"), ("jerk", "out_jerk"), ("v", "out_v"),
-                       ("qf", "out_qf"), ("p_lie", "out_p_lie")):
-            d = np.abs(V[f] - np.asarray(g[key][k]).reshape(-1)).max()
-            worst[f] = max(worst.get(f, 0.0), d)
-            assert d < 1e-9, (k, f, d)
+        compare_state_with_trace(state_view(lay, S), g, k, worst)      # the reference first: the independent check is the one that fires
+        compare_record_with_host_mirror(rec, N, shadow, k, set_tol=set_tol, need_sets=need_sets)      # the MPCData record (boundmpcmsg/msg/MPCData.msg)
+    return worst
+
+
+@pytest.mark.parametrize("fixture", ["closed_loop.npz", "closed_loop_n15.npz", "closed_loop_fail.npz", "closed_loop_patch.npz",
+                                     "closed_loop_scene.npz"])
+def test_replay_of_the_reference_trace(golden_dir, fixture):
+    """(scenarios: see tests/test_closed_loop.py TRACES)"""
+    g = np.load(os.path.join(golden_dir, fixture))
+    worst = replay_trace(g)
     assert g["switch"].sum() >= 1 and g["sector"][-1] >= 1      # the trace exercises a switch + via-point adaptation
     if "fail" in fixture:
         assert g["error_count"].max() == 2 and (g["status"] != 0).sum() == 3
