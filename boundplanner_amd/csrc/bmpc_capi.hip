@@ -6,11 +6,11 @@
 #include "bmpc_handle.hpp"
 #include "bmpc_internal.hpp"
 #include "bmpc_staging.hpp"
+#include "bmpc_debug_step.hpp"
 
 #include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <optional>
 #include <vector>
 
 using namespace bmpc;
@@ -583,129 +583,46 @@ extern "C" int bmpc_debug_inst_state(bmpc_handle* h, int B, double* out) {
     return 0;
 }
 
-// The two test entries (include/boundmpc.h).  Host pointers; the call owns the handle's workspace and stream and waits for the result.
-// What both do before they touch their arrays -- `refusal`: what the entry found wrong with its arguments (null: nothing); `busy`
-// holds the handle for the entry from here on.
-static int debug_prologue(bmpc_handle* h, int B, const char* name, const char* refusal, std::optional<BusyGuard>& busy) {
-    const std::string what = std::string(name) + ": ";
-    if (refusal) { if (h) h->err = what + refusal; return 1; }
+// The test entry (include/boundmpc.h): one super-step from a planted state, stopped where the requested outputs say.  Host pointers;
+// the call owns the handle's workspace and stream and waits for the result.
+extern "C" int bmpc_debug_superstep(bmpc_handle* h, int B, const bmpc_debug_step* s) {
+    auto refuse = [&](const char* why) { h->err = std::string("bmpc_debug_superstep: ") + why; return 1; };
+    if (!h) return 1;
+    if (const char* why = bmpc_debug_step_refusal(B, s)) return refuse(why);
+    if (s->ls && h->o.trial_repeats < 9) return refuse("needs a handle whose line search ends inside one launch (trial_repeats >= 9)");
     int rc = bmpc_wait(h);
     if (rc) return rc;
-    busy.emplace(h);
-    if (!busy->ok) return 4;
+    BUSY_OR_FAIL(h, "bmpc_debug_superstep");
     WEDGED_FAIL(h);
     HIPCHK(h, hipSetDevice(h->o.device));
-    if (h->o.hess != 2) { h->err = what + "needs a handle with the exact Hessian (hess = 2)"; return 1; }
+    if (h->o.hess != 2) return refuse("needs a handle with the exact Hessian (hess = 2)");
     if ((rc = pipe_ensure(h, B))) return rc;
-    if (B > h->pipe_cap) { h->err = what + "more instances than workspace slots"; return 1; }
-    return 0;
-}
-
-// the stage matrices of B instances at given points, rows and adjoint multipliers
-extern "C" int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                         const double* t, const double* z, const double* lam_pi, double* H) {
-    const bool bad = !h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !lam_pi || !H;
-    std::optional<BusyGuard> busy;
-    if (int rc = debug_prologue(h, B, "bmpc_debug_stage_matrices", bad ? "bad argument" : nullptr, busy)) return rc;
-    const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT;
-    double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
-    int *iters = nullptr, *status = nullptr;
-    Staging s;
-    s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
-    s.in(&t, rows); s.in(&z, rows); s.in(&lam_pi, B * N * 3);
-    s.out(&H, B * (N - 1) * NZ * NZ);
-    s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
-    const hipStream_t st = h->stream;
-    return s.run(h, st, [&]() -> int {
-        PipeArgsH A = pipe_args(h, B);
-        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
-        A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
-        if (int r = pipe_seed(h, A, B, st)) return r;
-        HIPCHK(h, bmpc_pipe_launch_stage_matrices(&A, t, z, lam_pi, H, st));
-        return 0;
-    });
-}
-
-// one super-step's Newton step of B instances from given points and rows
-extern "C" int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                      const double* t, const double* z, const int* mode, double* dzeta, double* dt, double* dz, double* state) {
-    const char* refusal = nullptr;
-    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !t || !z || !mode || !dzeta || !dt || !dz || !state) refusal = "bad argument";
-    else for (int i = 0; i < B; i++) if (mode[i] < 0 || mode[i] > 2) refusal = "mode must be 0, 1 or 2";
-    std::optional<BusyGuard> busy;
-    if (int rc = debug_prologue(h, B, "bmpc_debug_newton_step", refusal, busy)) return rc;
-    const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT;
-    double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
-    int *iters = nullptr, *status = nullptr;
-    Staging s;
-    s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
-    s.in(&t, rows); s.in(&z, rows); s.in(&mode, (size_t)B);
-    s.out(&dzeta, B * (N - 1) * NZ); s.out(&dt, rows); s.out(&dz, rows); s.out(&state, (size_t)B * 12);
-    s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
-    const hipStream_t st = h->stream;
-    return s.run(h, st, [&]() -> int {
-        PipeArgsH A = pipe_args(h, B);
-        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
-        A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
-        if (int r = pipe_seed(h, A, B, st)) return r;
-        HIPCHK(h, bmpc_pipe_launch_newton_step(&A, t, z, mode, dzeta, dt, dz, state, st));
-        return 0;
-    });
-}
-
-// one super-step's Newton step and line search of B instances from given points, rows and line-search state; with want_ctl the
-// iteration-control state is planted (ctl_plant, may be null) and returned (ctl): what the Riccati kernel's control and ls_decide made
-// of it, with the handle's own tol, max_iter, hess_switch, inertia_err, stall_n, gn_backoff, mu_floor_k, dw0
-static int debug_line_search(bmpc_handle* h, const char* name, bool want_ctl, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                      const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
-                                      double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                                      double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl) {
-    const char* refusal = nullptr;
-    if (!h || B <= 0 || !x0 || !lbx || !ubx || !p || !dzeta || !dt || !dz || !state || !zeta0 || !t0 || !z0 || !zeta1 || !t1 || !z1 || !ls || (want_ctl && !ctl))
-        refusal = "bad argument";
-    else if ((t == nullptr) != (z == nullptr) || (t == nullptr) != (mode == nullptr)) refusal = "t, z and mode are given together or not at all";
-    else if (!t && (plant0 || plant1 || ctl_plant)) refusal = "state is planted with given rows only";
-    else if (mode) for (int i = 0; i < B; i++) if (mode[i] < 0 || mode[i] > 2) refusal = "mode must be 0, 1 or 2";
-    if (!refusal && h->o.trial_repeats < 9) refusal = "needs a handle whose line search ends inside one launch (trial_repeats >= 9)";
-    std::optional<BusyGuard> busy;
-    if (int rc = debug_prologue(h, B, name, refusal, busy)) return rc;
-    int np0 = 0, np1 = 0, nls = 0;
+    if (B > h->pipe_cap) return refuse("more instances than workspace slots");
+    int np0 = 0, np1 = 0, nls = 0, npc = 0, nctl = 0;
     bmpc_pipe_ls_sizes(&np0, &np1, &nls);
-    int npc = 0, nctl = 0;
     bmpc_pipe_ctl_sizes(&npc, &nctl);
     const size_t N = (size_t)h->o.N, n_w = 44 * N + 6, rows = B * (N - 1) * NSLOT, nz = B * (N - 1) * NZ;
+    bmpc_debug_step d = *s;                                  // the record with device pointers, once run() has staged it
     double *x = nullptr, *f = nullptr, *viol = nullptr;      // of the argument block: never written here
     int *iters = nullptr, *status = nullptr;
-    Staging s;
-    s.in(&x0, B * n_w); s.in(&lbx, B * n_w); s.in(&ubx, B * n_w); s.in(&p, (size_t)B * NPAR);
-    s.in(&t, rows); s.in(&z, rows); s.in(&mode, (size_t)B); s.in(&plant0, (size_t)B * np0); s.in(&plant1, (size_t)B * np1); s.in(&ctl_plant, (size_t)B * npc);
-    s.out(&dzeta, nz); s.out(&dt, rows); s.out(&dz, rows); s.out(&state, (size_t)B * 12);
-    s.out(&zeta0, nz); s.out(&t0, rows); s.out(&z0, rows); s.out(&zeta1, nz); s.out(&t1, rows); s.out(&z1, rows); s.out(&ls, (size_t)B * nls); s.out(&ctl, (size_t)B * nctl);
-    s.scratch(&x, B * n_w); s.scratch(&f, (size_t)B); s.scratch(&viol, (size_t)B); s.scratch(&iters, (size_t)B); s.scratch(&status, (size_t)B);
+    Staging g;
+    g.in(&d.x0, B * n_w); g.in(&d.lbx, B * n_w); g.in(&d.ubx, B * n_w); g.in(&d.p, (size_t)B * NPAR);
+    g.in(&d.t, rows); g.in(&d.z, rows); g.in(&d.mode, (size_t)B);
+    g.in(&d.plant0, (size_t)B * np0); g.in(&d.plant1, (size_t)B * np1); g.in(&d.ctl_plant, (size_t)B * npc); g.in(&d.lam_pi, B * N * 3);
+    g.out(&d.H, nz * NZ);
+    g.out(&d.dzeta, nz); g.out(&d.dt, rows); g.out(&d.dz, rows); g.out(&d.state, (size_t)B * 12);
+    g.out(&d.zeta0, nz); g.out(&d.t0, rows); g.out(&d.z0, rows); g.out(&d.zeta1, nz); g.out(&d.t1, rows); g.out(&d.z1, rows);
+    g.out(&d.ls, (size_t)B * nls); g.out(&d.ctl, (size_t)B * nctl);
+    g.scratch(&x, B * n_w); g.scratch(&f, (size_t)B); g.scratch(&viol, (size_t)B); g.scratch(&iters, (size_t)B); g.scratch(&status, (size_t)B);
     const hipStream_t st = h->stream;
-    return s.run(h, st, [&]() -> int {
+    return g.run(h, st, [&]() -> int {
         PipeArgsH A = pipe_args(h, B);
-        A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.p = p;
+        A.x0 = d.x0; A.lbx = d.lbx; A.ubx = d.ubx; A.p = d.p;
         A.x = x; A.f = f; A.viol = viol; A.g = nullptr; A.iters = iters; A.status = status;
         if (int r = pipe_seed(h, A, B, st)) return r;
-        HIPCHK(h, bmpc_pipe_launch_line_search(&A, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0, t0, z0, zeta1, t1, z1, ls, st, ctl_plant, ctl));
+        HIPCHK(h, bmpc_pipe_launch_superstep(&A, &d, st));
         return 0;
     });
-}
-
-extern "C" int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                      const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
-                                      double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                                      double* zeta1, double* t1, double* z1, double* ls) {
-    return debug_line_search(h, "bmpc_debug_line_search", false, B, x0, lbx, ubx, p, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0, t0, z0,
-                             zeta1, t1, z1, ls, nullptr, nullptr);
-}
-extern "C" int bmpc_debug_iteration_control(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                            const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
-                                            double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                                            double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl) {
-    return debug_line_search(h, "bmpc_debug_iteration_control", true, B, x0, lbx, ubx, p, t, z, mode, plant0, plant1, dzeta, dt, dz, state, zeta0,
-                             t0, z0, zeta1, t1, z1, ls, ctl_plant, ctl);
 }
 
 // diagnostic / measurement: HIP events around every launch of the Riccati kernel (bmpc_k_ric: the throughput variant, bmpc_k_ric_lat:
@@ -731,6 +648,8 @@ extern "C" int bmpc_debug_ric_stats(bmpc_handle* h, double* out6) {
 
 extern "C" int bmpc_debug_ric_stats_full(bmpc_handle* h, double* out3) {
     if (!h || !out3) return 1;
+    int rc = bmpc_wait(h);
+    if (rc) return rc;
     for (int i = 0; i < 3; i++) out3[i] = h->ric_full[i];
     return 0;
 }

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 struct bmpc_handle;
+struct bmpc_debug_step;      // include/boundmpc.h
 namespace bmpc {
 struct RobotConst;
 struct IkOpts;
@@ -43,17 +44,9 @@ hipError_t bmpc_pipe_launch_retire_out(const bmpc::PipeArgsH* A, int n_max, hipS
 hipError_t bmpc_pipe_launch_retire_admit(const bmpc::PipeArgsH* A, int n_max, int refill, hipStream_t st);
 hipError_t bmpc_pipe_launch_step(bmpc::PipeArgsH* A, int n_act, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int* was_lat);
 hipError_t bmpc_pipe_launch_mult(const bmpc::PipeArgsH* A, hipStream_t st);
-hipError_t bmpc_pipe_launch_stage_matrices(const bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
-                                           double* d_H, hipStream_t st);
-hipError_t bmpc_pipe_launch_newton_step(bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode, double* d_dzeta,
-                                        double* d_dt, double* d_dz, double* d_state, hipStream_t st);
-hipError_t bmpc_pipe_launch_line_search(bmpc::PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode,
-                                        const double* d_plant0, const double* d_plant1, double* d_dzeta, double* d_dt, double* d_dz,
-                                        double* d_state, double* d_zeta0, double* d_t0, double* d_z0, double* d_zeta1, double* d_t1,
-                                        double* d_z1, double* d_ls, hipStream_t st, const double* d_ctl_plant = nullptr,
-                                        double* d_ctl = nullptr);      // (the last two: bmpc_debug_iteration_control)
-void bmpc_pipe_ls_sizes(int* plant0, int* plant1, int* out);      // doubles per instance: the two planted records, the returned state
-void bmpc_pipe_ctl_sizes(int* plant, int* out);                   // the same of bmpc_debug_iteration_control
+hipError_t bmpc_pipe_launch_superstep(bmpc::PipeArgsH* A, const bmpc_debug_step* d, hipStream_t st);      // (d: DEVICE pointers)
+void bmpc_pipe_ls_sizes(int* plant0, int* plant1, int* out);      // doubles per instance: plant0, plant1, ls of bmpc_debug_step
+void bmpc_pipe_ctl_sizes(int* plant, int* out);                   // ... ctl_plant, ctl
 long bmpc_pipe_fixed_launches(void);      // launches of this process that went to a fixed-horizon pair kernel (below)
 void bmpc_pipe_build_table(int* tbl);
 // bmpc_pair_n20.hip, bmpc_pair_n30.hip (bmpc_pair_fixed.hpp): the pair kernels of a super-step compiled for one horizon, slot-major

@@ -1064,7 +1064,8 @@ BMPC_KBODY void k_points_body(const AT& A, int wave, int lane, LDSD* lds_par) {
 
 // ------------------------------------------------------------------------------------------
 // k_curv: second-order kinematic terms of the Lagrangian Hessian (record fields F_CQQ, F_CQD) for the
-// instances in hess_mode (the list k_points built: wavefronts made of such instances only); forces from k_eval.
+// instances in hess_mode (the list k_points built: wavefronts made of such instances only); forces (PT_FORCE) from k_pose and
+// k_points, the sigmoid terms (PT_SIG) from k_pose.
 // ------------------------------------------------------------------------------------------
 template <class AT>
 BMPC_KBODY void k_curv_body(const AT& A, int wave, int lane, LDSD* lds) {
@@ -1092,7 +1093,7 @@ BMPC_KBODY void k_curv_body(const AT& A, int wave, int lane, LDSD* lds) {
     for (int c = 0; c < 6; c++)
         BMPC_UNROLL
         for (int a = 0; a < 3; a++) Fc[c][a] = F[(size_t)(9 + 3 * c + a) * A.NP];
-    // exact curvature of the sigmoid-weighted error terms (scalars from k_eval), chained through d(pose)/d(q, dq, pi)
+    // exact curvature of the sigmoid-weighted error terms (scalars from k_pose), chained through d(pose)/d(q, dq, pi)
     double sa[7], sbq[7], sbdq[7], sc1;
     {
         GCD Sg = A.part + (size_t)PT_SIG * A.NP + m.pi;

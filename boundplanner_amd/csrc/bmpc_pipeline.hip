@@ -11,6 +11,7 @@
 #include "bmpc_ric_kernel.hpp"
 #include "bmpc_stage_matrix.hpp"
 #include "bmpc_internal.hpp"
+#include "../../include/boundmpc.h"
 
 using namespace bmpc;
 
@@ -46,6 +47,8 @@ __global__ __launch_bounds__(64, 1) void bmpc_k_points_pose(PipeArgsH H, int nw)
     if ((int)blockIdx.x < nw) k_points_body(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
     else k_pose_body(DV(H), (int)blockIdx.x - nw, threadIdx.x, (LDSD*)bmpc_dyn_lds);
 }
+// What lets k_eval and k_curv share a grid: k_curv reads nothing k_eval writes -- the iterate, the curvature list (k_points) and the
+// partials PT_FORCE (k_pose, k_points) and PT_SIG (k_pose), all complete before this launch -- and writes record fields of its own.
 __global__ __launch_bounds__(64, 1) void bmpc_k_eval_curv(PipeArgsH H, int nw) {
     if ((int)blockIdx.x < nw) k_eval_body<0>(DV(H), blockIdx.x, threadIdx.x, (LDSD*)bmpc_dyn_lds);
     else k_curv_body(DV(H), (int)blockIdx.x - nw, threadIdx.x, (LDSD*)bmpc_dyn_lds);
@@ -271,7 +274,7 @@ extern "C" hipError_t bmpc_pipe_launch_mult(const PipeArgsH* A, hipStream_t st) 
     return hipGetLastError();
 }
 
-// test entry bmpc_debug_stage_matrices (bmpc_stage_matrix.hpp): kernels of their own beside the product's, which they do not touch
+// test entry bmpc_debug_superstep (bmpc_stage_matrix.hpp): kernels of their own beside the product's, which they do not touch
 __global__ __launch_bounds__(64) void bmpc_k_dbg_set_rows(PipeArgsH H, const double* t, const double* z, const int* mode) {
     k_set_rows_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)t, (GCD)z, (GCI)mode);
 }
@@ -282,35 +285,6 @@ __global__ __launch_bounds__(BMPC_RIC_NT, 1) void bmpc_k_dbg_stage_matrices(Pipe
     __shared__ __attribute__((aligned(16))) double lds[RIC_LDS_DOUBLES];
     k_stage_matrix_body<BMPC_RIC_NT>(ric_kernel_args(), blockIdx.x, threadIdx.x, (LDSD*)lds, (GCD)lam_pi, (GD)Hout);
 }
-// B instances in slots 0 .. B-1, just initialised (bmpc_pipe_launch_init): rows overwritten, the super-step's own evaluation
-// launches once, then the stage matrices
-extern "C" hipError_t bmpc_pipe_launch_stage_matrices(const PipeArgsH* A, const double* d_t, const double* d_z, const double* d_lam_pi,
-                                                      double* d_H, hipStream_t st) {
-    const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
-    hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_t, d_z, (const int*)nullptr);
-    launch_eval(A, waves_for(A->N, A->B), st);
-    hipLaunchKernelGGL(bmpc_k_dbg_stage_matrices, dim3(A->B), dim3(BMPC_RIC_NT), 0, st, *A, d_lam_pi, d_H);
-    return hipGetLastError();
-}
-
-// test entry bmpc_debug_newton_step: B instances in slots 0 .. B-1, just initialised; rows and the Hessian mode overwritten, then
-// the evaluation and the factorisation / direction launches of a super-step exactly as bmpc_pipe_launch_step issues them for B
-// live instances -- no trial, no rotate -- and the copy-out
-extern "C" hipError_t bmpc_pipe_launch_newton_step(PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode, double* d_dzeta,
-                                                   double* d_dt, double* d_dz, double* d_state, hipStream_t st) {
-    const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
-    const int nw = waves_for(A->N, A->B);
-    hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_t, d_z, d_mode);
-    launch_eval(A, nw, st);
-    launch_direction(A, A->B, nw, st, nullptr, nullptr, nullptr);
-    hipLaunchKernelGGL(bmpc_k_dbg_newton_out, dim3((unsigned)((nset + 63) / 64)), dim3(64), 0, st, *A, d_dzeta, d_dt, d_dz, d_state);
-    return hipGetLastError();
-}
-
-// test entry bmpc_debug_line_search: the sequence of bmpc_pipe_launch_newton_step (rows and mode overwritten only when rows are
-// given), then the line search exactly as bmpc_pipe_launch_step issues it for B live instances (launch_trial) -- no rotate -- and the
-// copy-out.  Line-search state is planted before the evaluation launches (with a NaN in the copies the trial writes, when rows are
-// given) and after k_step.
 __global__ __launch_bounds__(64) void bmpc_k_dbg_ls_plant(PipeArgsH H, const double* plant, int after_step, int nan_other) {
     k_ls_plant_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)plant, after_step, nan_other);
 }
@@ -318,34 +292,38 @@ __global__ __launch_bounds__(64) void bmpc_k_dbg_ls_out(PipeArgsH H, double* zet
                                                         double* z1, double* ls) {
     k_ls_out_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GD)zeta0, (GD)t0, (GD)z0, (GD)zeta1, (GD)t1, (GD)z1, (GD)ls);
 }
-// test entry bmpc_debug_iteration_control: the same sequence with the iteration-control state planted per instance before the
-// evaluation launches and copied out after the direction launches and after the trial launch (d_ctl_plant, d_ctl: null = neither)
 __global__ __launch_bounds__(64) void bmpc_k_dbg_ctl_plant(PipeArgsH H, const double* plant) {
     k_ctl_plant_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GCD)plant);
 }
 __global__ __launch_bounds__(64) void bmpc_k_dbg_ctl_out(PipeArgsH H, double* ctl, int after_trial) {
     k_ctl_out_body(DV(H), (size_t)blockIdx.x * 64 + threadIdx.x, (GD)ctl, after_trial);
 }
-extern "C" hipError_t bmpc_pipe_launch_line_search(PipeArgsH* A, const double* d_t, const double* d_z, const int* d_mode,
-                                                   const double* d_plant0, const double* d_plant1, double* d_dzeta, double* d_dt,
-                                                   double* d_dz, double* d_state, double* d_zeta0, double* d_t0, double* d_z0,
-                                                   double* d_zeta1, double* d_t1, double* d_z1, double* d_ls, hipStream_t st,
-                                                   const double* d_ctl_plant, double* d_ctl) {
-    const unsigned nbi = (unsigned)((A->B + 63) / 64);
-    const size_t nset = (size_t)A->B * (A->N - 1) * NSLOT;
-    const unsigned nb = (unsigned)((nset + 63) / 64);
+// B instances in slots 0 .. B-1, just initialised (bmpc_pipe_launch_init); d: the entry's record with device pointers, which
+// bmpc_debug_superstep has checked.  State planted, then the evaluation, the factorisation / direction and the trial launches of a
+// super-step exactly as bmpc_pipe_launch_step issues them for B live instances, as far as the requested outputs reach -- no rotate --
+// with a copy-out after each.  The line-search state (and the NaN in the copies the trial writes, when rows are given) is planted
+// only when the trial runs.
+extern "C" hipError_t bmpc_pipe_launch_superstep(PipeArgsH* A, const bmpc_debug_step* d, hipStream_t st) {
+    const unsigned nbi = (unsigned)((A->B + 63) / 64);                                      // one thread per instance
+    const unsigned nb = (unsigned)(((size_t)A->B * (A->N - 1) * NSLOT + 63) / 64);          // ... per (instance, stage, slot)
     const int nw = waves_for(A->N, A->B);
-    if (d_t) hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3(nb), dim3(64), 0, st, *A, d_t, d_z, d_mode);
-    if (d_t || d_plant0) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d_plant0, 0, d_t ? 1 : 0);
-    if (d_ctl_plant) hipLaunchKernelGGL(bmpc_k_dbg_ctl_plant, dim3(nbi), dim3(64), 0, st, *A, d_ctl_plant);
+    const bool trial = d->ls != nullptr;
+    if (d->t) hipLaunchKernelGGL(bmpc_k_dbg_set_rows, dim3(nb), dim3(64), 0, st, *A, d->t, d->z, d->H ? (const int*)nullptr : d->mode);
+    if (trial && (d->t || d->plant0)) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d->plant0, 0, d->t ? 1 : 0);
+    if (d->ctl_plant) hipLaunchKernelGGL(bmpc_k_dbg_ctl_plant, dim3(nbi), dim3(64), 0, st, *A, d->ctl_plant);
     launch_eval(A, nw, st);
+    if (d->H) {
+        hipLaunchKernelGGL(bmpc_k_dbg_stage_matrices, dim3(A->B), dim3(BMPC_RIC_NT), 0, st, *A, d->lam_pi, d->H);
+        return hipGetLastError();
+    }
     launch_direction(A, A->B, nw, st, nullptr, nullptr, nullptr);
-    hipLaunchKernelGGL(bmpc_k_dbg_newton_out, dim3(nb), dim3(64), 0, st, *A, d_dzeta, d_dt, d_dz, d_state);
-    if (d_ctl) hipLaunchKernelGGL(bmpc_k_dbg_ctl_out, dim3(nbi), dim3(64), 0, st, *A, d_ctl, 0);
-    if (d_plant1) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d_plant1, 1, 0);
+    hipLaunchKernelGGL(bmpc_k_dbg_newton_out, dim3(nb), dim3(64), 0, st, *A, d->dzeta, d->dt, d->dz, d->state);
+    if (d->ctl) hipLaunchKernelGGL(bmpc_k_dbg_ctl_out, dim3(nbi), dim3(64), 0, st, *A, d->ctl, 0);
+    if (!trial) return hipGetLastError();
+    if (d->plant1) hipLaunchKernelGGL(bmpc_k_dbg_ls_plant, dim3(nb), dim3(64), 0, st, *A, d->plant1, 1, 0);
     launch_trial(A, nw, st);
-    hipLaunchKernelGGL(bmpc_k_dbg_ls_out, dim3(nb), dim3(64), 0, st, *A, d_zeta0, d_t0, d_z0, d_zeta1, d_t1, d_z1, d_ls);
-    if (d_ctl) hipLaunchKernelGGL(bmpc_k_dbg_ctl_out, dim3(nbi), dim3(64), 0, st, *A, d_ctl, 1);
+    hipLaunchKernelGGL(bmpc_k_dbg_ls_out, dim3(nb), dim3(64), 0, st, *A, d->zeta0, d->t0, d->z0, d->zeta1, d->t1, d->z1, d->ls);
+    if (d->ctl) hipLaunchKernelGGL(bmpc_k_dbg_ctl_out, dim3(nbi), dim3(64), 0, st, *A, d->ctl, 1);
     return hipGetLastError();
 }
 

@@ -63,8 +63,8 @@ constexpr int KREC = 320;               // gains per pair: K (9x32) + kf (2x16)
 constexpr int RIC_NATT = 5 /* at most; PipeArgs.natt of them run */, RIC_FS_P0 = 24 * 25 / 2, RIC_FS_P = NPSYM - RIC_FS_P0, RIC_FS = 256;
 static_assert(8 + RIC_FS_P + 16 <= RIC_FS, "forward-start record");
 constexpr int NPART = 272;              // per-pair partial sums (16) + forces for k_curv (27) + point-group results (121) + PT_SIG (10) + pose-row results (88)
-constexpr int PT_FORCE = 16;            // Fp[3], Fv[6], Fc[6][3]
-constexpr int PT_SIG = 169;             // k_eval -> k_curv: c1 = 2 sig sig'' |e|^2, dpp[3], 2 sig sig' De^T e [6] (exact curvature of sig^2 |e|^2)
+constexpr int PT_FORCE = 16;            // k_pose (Fp, Fv), k_points (Fc) -> k_curv: Fp[3], Fv[6], Fc[6][3]
+constexpr int PT_SIG = 169;             // k_pose -> k_curv: c1 = 2 sig sig'' |e|^2, dpp[3], 2 sig sig' De^T e [6] (exact curvature of sig^2 |e|^2)
 // results of the collision-point rows (k_points), read by k_eval where it needs them
 constexpr int PT_SIDE = 48, SD_CD = 0 /*[5][7]*/, SD_CD5 = 35 /*7*/, SD_HQQ = 42 /*28*/, SD_GQ = 70 /*[3][7]*/,
               SD_DD = 91 /*6*/, SD_GD = 97 /*[3][6]*/, SD_KKT = 115 /*cmax csum cmin zsum prim nrows*/, SD_END = 121;

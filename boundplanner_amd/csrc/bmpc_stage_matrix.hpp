@@ -1,14 +1,15 @@
-// bmpc_stage_matrix.hpp -- test entry (bmpc_debug_stage_matrices, tests/emu/emu_pipe.cpp): the stage matrices the Riccati sweep
-// factorises, at a given point with given row slacks / multipliers and given adjoint multipliers of the pi dynamics.  Two bodies
-// beside the product's kernels, none of which changes: k_set_rows_body writes (t, z) over the ones the init launch left and switches
-// the exact Hessian on; after the product's evaluation kernels have run once, k_stage_matrix_body runs the sweep's own load phase
-// (ric_phase_load_impl) per stage and copies the matrix it leaves in LDS.  tests/test_hessian_pin*.py compare the result with the
-// reference-derived probes of tests/golden/hess_N*.npz.  The second test entry, bmpc_debug_newton_step, shares k_set_rows_body
-// and adds k_newton_out_body, which copies out what the product's own Riccati, forward and row-step kernels left.  The third,
-// bmpc_debug_line_search, adds k_ls_plant_body (line-search state planted per instance, NaN in the copies the trial writes) and
-// k_ls_out_body (the iterate before and after the search, the line-search state).  The fourth, bmpc_debug_iteration_control, runs
-// the third's sequence with k_ctl_plant_body (iteration-control state planted per instance) and k_ctl_out_body (what the Riccati
-// kernel's control and ls_decide left of it).
+// bmpc_stage_matrix.hpp -- the bodies of the test entry bmpc_debug_superstep (include/boundmpc.h) beside the product's kernels, none
+// of which changes; bmpc_pipe_launch_superstep (bmpc_pipeline.hip) and Rig::superstep (tests/emu/emu_pipe.cpp) run them in one
+// sequence, one super-step from a planted state:
+//   init launch -> k_set_rows_body (t, z written over the ones the init launch left, the first attempt's Hessian mode)
+//     -> k_ls_plant_body (line-search state before the evaluation, NaN in the copies the trial writes) -> k_ctl_plant_body
+//     (iteration-control state) -> the product's evaluation kernels
+//     -> k_stage_matrix_body: the sweep's own load phase (ric_phase_load_impl) per stage, the matrix it leaves in LDS copied out; stop
+//        (tests/test_hessian_pin*.py compare it with the reference-derived probes of tests/golden/hess_N*.npz)
+//     -> the product's Riccati, forward and row-step kernels -> k_newton_out_body (what they left) -> k_ctl_out_body (what the Riccati
+//        kernel's control left of the iteration-control state); stop, or
+//     -> k_ls_plant_body (line-search state after k_step) -> the product's trial kernel -> k_ls_out_body (the iterate before and after
+//        the search, the line-search state) -> k_ctl_out_body (what ls_decide left).
 #pragma once
 #include "bmpc_ric_kernel.hpp"
 
@@ -36,7 +37,7 @@ BMPC_INL void k_set_rows_body(const PipeArgs& A, size_t e, GCD t, GCD z, GCI mod
     }
 }
 
-// Test entry bmpc_debug_newton_step (tests/test_newton_step*.py): what one super-step's k_ric / k_fwd / k_step left in the
+// The Newton step (tests/test_newton_step*.py): what one super-step's k_ric / k_fwd / k_step left in the
 // workspace, one thread per (instance row, stage, slot).  dzeta [B][N-1][NZ]; dt, dz [B][N-1][NSLOT]: dt = c - t with k_step's
 // stored c = t + dt, dz = (mu - z c) / t as StepVisitor::fin and k_trial form it (NaN in the slots k_step did not write);
 // state [B][12]: the fields of bmpc_debug_inst_state.
@@ -60,7 +61,7 @@ BMPC_INL void k_newton_out_body(const PipeArgs& A, size_t e, GD dzeta, GD dt, GD
     }
 }
 
-// Test entry bmpc_debug_line_search (tests/test_line_search*.py).  Doubles per instance of the two planted records and of the
+// The line search (tests/test_line_search*.py).  Doubles per instance of the two planted records and of the
 // returned line-search state:
 //   plant, before the evaluation launches [LS_PLANT0]: f0, th0, ls0, it, filt_mu, nfilt, filt_th[8], filt_phi[8]
 //   plant, after k_step                   [LS_PLANT1]: nfilt, filt_th[8], filt_phi[8], theta_max, theta_min
@@ -141,7 +142,7 @@ BMPC_INL void k_ls_out_body(const PipeArgs& A, size_t e, GD zeta0, GD t0, GD z0,
     }
 }
 
-// Test entry bmpc_debug_iteration_control (tests/test_iteration_control*.py).  Doubles per instance of the planted record and of the
+// The iteration control (tests/test_iteration_control*.py).  Doubles per instance of the planted record and of the
 // returned control state:
 //   plant, before the evaluation launches [CTL_PLANT]: mu, err_prev, err_best, stall, dw_last, gn_back, gn_skip, it
 //   state [CTL_OUT], after the direction launches:     state, status (-1: not finished), mu, hreg, tries, ksel, hess_mode, err_prev,

@@ -70,10 +70,52 @@ class BmpcOpts(ctypes.Structure):
                 ("trial_repeats", ctypes.c_int), ("watchdog_ms", ctypes.c_int), ("max_batch", ctypes.c_int), ("pool_slots", ctypes.c_int)]
 
 
+class BmpcDebugStep(ctypes.Structure):
+    """bmpc_debug_step of include/boundmpc.h: the arguments of bmpc_debug_superstep."""
+    _fields_ = [(k, _ip if k == "mode" else _dp) for k in
+                ("x0", "lbx", "ubx", "p", "t", "z", "mode", "plant0", "plant1", "ctl_plant", "lam_pi", "H", "dzeta", "dt", "dz", "state",
+                 "zeta0", "t0", "z0", "zeta1", "t1", "z1", "ls", "ctl")]
+
+
+# The record's arrays for a batch of B at horizon N, name -> shape: the inputs beside mode (int32 [B]), and the outputs.
+STEP_IN = lambda B, N: dict(x0=(B, 44 * N + 6), lbx=(B, 44 * N + 6), ubx=(B, 44 * N + 6), p=(B, 875), t=(B, N - 1, 208), z=(B, N - 1, 208),
+                            plant0=(B, 22), plant1=(B, 19), ctl_plant=(B, 8), lam_pi=(B, N, 3))
+LS_SHAPES = lambda B, N: dict(dzeta=(B, N - 1, 41), dt=(B, N - 1, 208), dz=(B, N - 1, 208), state=(B, 12), zeta0=(B, N - 1, 41),
+                              t0=(B, N - 1, 208), z0=(B, N - 1, 208), zeta1=(B, N - 1, 41), t1=(B, N - 1, 208), z1=(B, N - 1, 208),
+                              ls=(B, 36), ctl=(B, 20), H=(B, N - 1, 41, 41))
+# The outputs to ask for, by where the sequence is to stop (a request bmpc_debug_superstep refuses is any other tuple of names).
+_LS = tuple(LS_SHAPES(1, 2))
+STOPS = {"H": ("H",), "newton": _LS[:4], "ls": _LS[:11], "ctl": _LS[:12]}
+
+
+def debug_step(N, want, **arrays):
+    """The arguments of bmpc_debug_superstep from named arrays (needs no GPU; tests/emu_pipe_lib.py uses it too): x0, lbx, ubx, p
+    and any of t, z, mode, plant0, plant1, ctl_plant, lam_pi (include/boundmpc.h; None = not given); want: the names of the outputs
+    to allocate, a tuple of STOPS.  +-inf bounds become +-1e20, mode is broadcast to int32 [B], everything is made contiguous and
+    its shape checked.  Returns (B, the filled BmpcDebugStep -- which keeps the arrays alive --, the dict of zeroed outputs)."""
+    a = {k: v for k, v in arrays.items() if v is not None}
+    a["lbx"] = np.where(np.isinf(a["lbx"]), -1e20, a["lbx"]); a["ubx"] = np.where(np.isinf(a["ubx"]), 1e20, a["ubx"])
+    for k in ("x0", "lbx", "ubx", "p"):
+        a[k] = np.atleast_2d(a[k])
+    B = a["x0"].shape[0]
+    shapes = STEP_IN(B, N)
+    for k in a:
+        if k == "mode":
+            a[k] = np.ascontiguousarray(np.broadcast_to(a[k], (B,)), np.int32)
+        else:
+            a[k] = np.ascontiguousarray(a[k], float)
+            assert a[k].shape == shapes[k], (k, a[k].shape, shapes[k])
+    shapes = LS_SHAPES(B, N)
+    out = {k: np.zeros(shapes[k]) for k in want}
+    step = BmpcDebugStep(**{k: v.ctypes.data_as(_ip if k == "mode" else _dp) for k, v in {**a, **out}.items()})
+    step.arrays = (a, out)
+    return B, step, out
+
+
 EXPORTS = ["bmpc_default_opts", "bmpc_create", "bmpc_destroy", "bmpc_last_error", "bmpc_dims",
            "bmpc_gbounds", "bmpc_solve", "bmpc_solve_dev", "bmpc_solve_dev_async", "bmpc_multipliers_dev", "bmpc_wait", "bmpc_active", "bmpc_fk",
            "bmpc_last_kernel_ms", "bmpc_get_opts", "bmpc_stream", "bmpc_robot_iiwa14", "bmpc_robot_gen3", "bmpc_set_robot", "bmpc_get_robot",
-           "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_stage_matrices", "bmpc_debug_newton_step", "bmpc_debug_line_search", "bmpc_debug_iteration_control", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full",
+           "bmpc_debug_phase_cycles", "bmpc_debug_spin", "bmpc_debug_inst_state", "bmpc_debug_superstep", "bmpc_debug_time_ric", "bmpc_debug_ric_stats", "bmpc_debug_ric_stats_full",
            "bmpc_loop_state_doubles", "bmpc_loop_log_doubles", "bmpc_loop_field", "bmpc_loop_create", "bmpc_loop_destroy",
            "bmpc_loop_last_error", "bmpc_loop_record_doubles", "bmpc_loop_set_record", "bmpc_loop_records", "bmpc_loop_set_obstacles", "bmpc_loop_set_scenes", "bmpc_loop_set_rollout_scenes", "bmpc_loop_upload", "bmpc_loop_download", "bmpc_loop_run", "bmpc_loop_run_async", "bmpc_loop_prepare",
            "bmpc_loop_solve", "bmpc_loop_finish", "bmpc_loop_problem", "bmpc_loop_solution", "bmpc_loop_set_solution",
@@ -136,10 +178,7 @@ def load_library():
         lib.bmpc_loop_set_solution.argtypes = [ctypes.c_void_p, _dp, _ip, _ip, _dp]
         lib.bmpc_debug_spin.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.bmpc_debug_inst_state.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp]
-        lib.bmpc_debug_stage_matrices.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 8
-        lib.bmpc_debug_newton_step.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 4
-        lib.bmpc_debug_line_search.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 13
-        lib.bmpc_debug_iteration_control.argtypes = [ctypes.c_void_p, ctypes.c_int] + [_dp] * 6 + [ctypes.POINTER(ctypes.c_int)] + [_dp] * 15
+        lib.bmpc_debug_superstep.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(BmpcDebugStep)]
         lib.bmpc_debug_time_ric.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.bmpc_debug_ric_stats.argtypes = [ctypes.c_void_p, _dp]
         lib.bmpc_debug_ric_stats_full.argtypes = [ctypes.c_void_p, _dp]
@@ -247,34 +286,22 @@ class HipBoundMPC:
         self._chk(self.lib.bmpc_debug_inst_state(self._h, int(B), _P(out)), "bmpc_debug_inst_state")
         return out
 
+    def _superstep(self, want, **arrays):
+        """bmpc_debug_superstep on the named arrays (debug_step): the dict of the outputs `want` names."""
+        B, step, out = debug_step(self.N, want, **arrays)
+        self._chk(self.lib.bmpc_debug_superstep(self._h, B, ctypes.byref(step)), "bmpc_debug_superstep")
+        return out
+
     def stage_matrices(self, x0, lbx, ubx, p, t, z, lam_pi):
         """Test entry: stage matrices H [B][N-1][41][41] (zeta coordinates) at the points x0 [B][n_w] for given row slacks /
-        multipliers t, z [B][N-1][208] and adjoint multipliers lam_pi [B][N][3] (bmpc_debug_stage_matrices)."""
-        lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-        x0, lbx, ubx, p, t, z, lam_pi = (np.ascontiguousarray(np.atleast_2d(a) if a.ndim < 2 else a, float) for a in (x0, lbx, ubx, p, t, z, lam_pi))
-        B, N = x0.shape[0], self.N
-        assert x0.shape == lbx.shape == ubx.shape == (B, 44 * N + 6) and p.shape == (B, 875)
-        assert t.shape == z.shape == (B, N - 1, 208) and lam_pi.shape == (B, N, 3)
-        H = np.zeros((B, N - 1, 41, 41))
-        self._chk(self.lib.bmpc_debug_stage_matrices(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z), _P(lam_pi), _P(H)),
-                  "bmpc_debug_stage_matrices")
-        return H
+        multipliers t, z [B][N-1][208] and adjoint multipliers lam_pi [B][N][3] (bmpc_debug_superstep stopped after the evaluation)."""
+        return self._superstep(STOPS["H"], x0=x0, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=1, lam_pi=lam_pi)["H"]
 
     def newton_step(self, x0, lbx, ubx, p, t, z, mode):
         """Test entry: the Newton step of one super-step at the points x0 [B][n_w] for given row slacks / multipliers t, z
         [B][N-1][208] and first-attempt Hessian mode [B] (0 Gauss-Newton, 1 exact, 2 exact + inertia correction on failure):
-        (dzeta [B][N-1][41], dt [B][N-1][208], dz [B][N-1][208], state [B][12]) (bmpc_debug_newton_step)."""
-        lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-        x0, lbx, ubx, p, t, z = (np.ascontiguousarray(np.atleast_2d(a) if a.ndim < 2 else a, float) for a in (x0, lbx, ubx, p, t, z))
-        B, N = x0.shape[0], self.N
-        mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
-        assert x0.shape == lbx.shape == ubx.shape == (B, 44 * N + 6) and p.shape == (B, 875)
-        assert t.shape == z.shape == (B, N - 1, 208)
-        dzeta, dt, dz, state = np.zeros((B, N - 1, 41)), np.zeros((B, N - 1, 208)), np.zeros((B, N - 1, 208)), np.zeros((B, 12))
-        self._chk(self.lib.bmpc_debug_newton_step(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z),
-                                                  mode.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _P(dzeta), _P(dt), _P(dz), _P(state)),
-                  "bmpc_debug_newton_step")
-        return dzeta, dt, dz, state
+        (dzeta [B][N-1][41], dt [B][N-1][208], dz [B][N-1][208], state [B][12]) (bmpc_debug_superstep stopped after the direction)."""
+        return tuple(self._superstep(STOPS["newton"], x0=x0, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=mode).values())
 
     LS_FIELDS = ("ap", "ad", "D", "phi0", "alpha", "bt", "f0", "th0", "ls0", "nfilt") + tuple(f"filt_th{j}" for j in range(8)) \
         + tuple(f"filt_phi{j}" for j in range(8)) + ("theta_max", "theta_min", "it", "flip", "hess_mode", "state", "mu", "filt_mu", "armijo", "pad")
@@ -284,51 +311,17 @@ class HipBoundMPC:
                   "gn_skip", "it", "fk", "it_after", "hess_mode_after", "gn_skip_after", "state_after", "pad")
 
     def line_search(self, x0, lbx, ubx, p, t=None, z=None, mode=None, plant0=None, plant1=None):
-        """Test entry: Newton step and filter line search of one super-step (bmpc_debug_line_search).  t, z [B][N-1][208] and
-        mode [B] as for newton_step, or all None (the rows of the init launch; nothing planted); plant0 [B][22], plant1 [B][19]
-        or None (include/boundmpc.h; NaN = leave the field).  Returns a dict: dzeta, dt, dz, state (as newton_step), zeta0, t0, z0,
-        zeta1, t1, z1, ls [B][36] (LS_FIELDS)."""
-        lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-        x0, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (x0, lbx, ubx, p))
-        B, N = x0.shape[0], self.N
-        assert x0.shape == lbx.shape == ubx.shape == (B, 44 * N + 6) and p.shape == (B, 875)
-        if t is not None:
-            t, z = (np.ascontiguousarray(a, float) for a in (t, z))
-            mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
-            assert t.shape == z.shape == (B, N - 1, 208)
-        if plant0 is not None:
-            plant0 = np.ascontiguousarray(plant0, float); assert plant0.shape == (B, 22)
-        if plant1 is not None:
-            plant1 = np.ascontiguousarray(plant1, float); assert plant1.shape == (B, 19)
-        shp = dict(dzeta=(B, N - 1, 41), dt=(B, N - 1, 208), dz=(B, N - 1, 208), state=(B, 12), zeta0=(B, N - 1, 41), t0=(B, N - 1, 208),
-                   z0=(B, N - 1, 208), zeta1=(B, N - 1, 41), t1=(B, N - 1, 208), z1=(B, N - 1, 208), ls=(B, 36))
-        out = {k: np.zeros(v) for k, v in shp.items()}
-        self._chk(self.lib.bmpc_debug_line_search(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z),
-                                                  mode.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if mode is not None else None,
-                                                  _P(plant0), _P(plant1), *(_P(out[k]) for k in shp)), "bmpc_debug_line_search")
-        return out
+        """Test entry: Newton step and filter line search of one super-step (bmpc_debug_superstep run through the trial).  t, z
+        [B][N-1][208] and mode [B] as for newton_step, or all None (the rows of the init launch; nothing planted); plant0 [B][22],
+        plant1 [B][19] or None (include/boundmpc.h; NaN = leave the field).  Returns a dict: dzeta, dt, dz, state (as newton_step),
+        zeta0, t0, z0, zeta1, t1, z1, ls [B][36] (LS_FIELDS)."""
+        return self._superstep(STOPS["ls"], x0=x0, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=mode, plant0=plant0, plant1=plant1)
 
     def iteration_control(self, x0, lbx, ubx, p, t, z, mode, ctl_plant=None, plant0=None, plant1=None):
         """Test entry: the sequence of line_search with the iteration-control state planted (ctl_plant [B][8], CTL_PLANT_FIELDS;
-        NaN = leave the field) and returned: the dict of line_search plus ctl [B][20] (CTL_FIELDS) (bmpc_debug_iteration_control)."""
-        lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-        x0, lbx, ubx, p, t, z = (np.ascontiguousarray(np.atleast_2d(a) if a.ndim < 2 else a, float) for a in (x0, lbx, ubx, p, t, z))
-        B, N = x0.shape[0], self.N
-        mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
-        assert x0.shape == lbx.shape == ubx.shape == (B, 44 * N + 6) and p.shape == (B, 875) and t.shape == z.shape == (B, N - 1, 208)
-        plants = []
-        for a, n in ((plant0, 22), (plant1, 19), (ctl_plant, 8)):
-            if a is not None:
-                a = np.ascontiguousarray(a, float); assert a.shape == (B, n)
-            plants.append(a)
-        shp = dict(dzeta=(B, N - 1, 41), dt=(B, N - 1, 208), dz=(B, N - 1, 208), state=(B, 12), zeta0=(B, N - 1, 41), t0=(B, N - 1, 208),
-                   z0=(B, N - 1, 208), zeta1=(B, N - 1, 41), t1=(B, N - 1, 208), z1=(B, N - 1, 208), ls=(B, 36), ctl=(B, 20))
-        out = {k: np.zeros(v) for k, v in shp.items()}
-        self._chk(self.lib.bmpc_debug_iteration_control(self._h, B, _P(x0), _P(lbx), _P(ubx), _P(p), _P(t), _P(z),
-                                                        mode.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _P(plants[0]), _P(plants[1]),
-                                                        *(_P(out[k]) for k in shp if k != "ctl"), _P(plants[2]), _P(out["ctl"])),
-                  "bmpc_debug_iteration_control")
-        return out
+        NaN = leave the field) and returned: the dict of line_search plus ctl [B][20] (CTL_FIELDS)."""
+        return self._superstep(STOPS["ctl"], x0=x0, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=mode, plant0=plant0, plant1=plant1,
+                               ctl_plant=ctl_plant)
 
     def time_ric(self, on=True):
         """HIP events around every launch of the Riccati kernel, from the next solve on (bmpc_debug_time_ric)."""

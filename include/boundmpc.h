@@ -233,63 +233,62 @@ int bmpc_debug_phase_cycles(bmpc_handle* h, double* out16);
  * retries, rejected line-search trials, KKT error of the previous iterate, stall counter.  With max_iter = k: the decisions of
  * iteration k - 1, which the iterate-for-iterate parity test compares with the oracle's.  B <= workspace slots. */
 int bmpc_debug_inst_state(bmpc_handle* h, int B, double* out);
-/* Test entry: the stage matrices the Riccati sweep factorises (zeta coordinates, H [B][N-1][41][41], row-major), for B instances
- * at the points x0 with GIVEN row slacks / multipliers t, z [B][N-1][208] (row slots of csrc/bmpc_device.hpp) and GIVEN adjoint
- * multipliers of the pi dynamics lam_pi [B][N][3] (stage k uses lam_pi[k+1]).  The slots are initialised by the product's init
- * launch, t, z and the exact-Hessian switch are overwritten, the product's evaluation launches of a super-step run once, and a
- * kernel of the entry's own runs the sweep's load phase per stage and copies the matrix out.  Host pointers; B <= workspace
- * slots; the handle must have been created with hess = 2.  tests/test_hessian_pin_gpu.py compares the result with probes of the
- * reference's Lagrangian Hessian. */
-int bmpc_debug_stage_matrices(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                              const double* t, const double* z, const double* lam_pi, double* H);
-/* Test entry: the Newton step of ONE super-step, for B instances at the points x0 with GIVEN row slacks / multipliers
- * t, z [B][N-1][208] (row slots of csrc/bmpc_device.hpp).  mode [B]: the Hessian of the first factorisation attempt -- 0 Gauss-Newton,
- * 1 exact, 2 exact with the KKT error of the previous iterate set to 0 (a failed attempt is then answered by delta_w, not by the
- * Gauss-Newton fallback).  Sequence: the product's init launch, rows and mode overwritten, the product's evaluation launches, the
- * product's Riccati launch in the variant B live instances select, k_fwd, k_step; no trial point, no list rotation.  Returned per
- * instance: dzeta [B][N-1][41]; the row steps dt, dz [B][N-1][208] (NaN in the slots k_step did not write: padding slots are left
- * untouched); state [B][12] with the fields of bmpc_debug_inst_state, where state[1] is -1 when the instance took a step and its
- * final status (0 converged at entry, 3 every factorisation attempt failed) otherwise, [2] the barrier parameter the forward start
- * used, [4] / [5] the dual / primal fraction-to-boundary lengths, [6] delta_w, [7] the mode the FIRST attempt ran with, [8] the
- * retries.  Host pointers; B <= workspace slots; the handle must have been created with hess = 2.  rc 1 on misuse. */
-int bmpc_debug_newton_step(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                           const double* t, const double* z, const int* mode, double* dzeta, double* dt, double* dz, double* state);
-/* Test entry: the Newton step AND the filter line search of ONE super-step.  Sequence: that of bmpc_debug_newton_step (init launch,
- * rows and mode overwritten, the evaluation launches, the Riccati launch, k_fwd, k_step), then the product's trial launch once, in
- * the variant the number of groups of pairs selects (bmpc_k_trial_spec / bmpc_k_trial); no list rotation.  The handle's
- * trial_repeats must be the default (>= 9): the whole search ends inside the launch.  t, z, mode as in bmpc_debug_newton_step, or
- * all three NULL: the rows stay as the init launch made them (the merit pieces are then those of the init launch) and nothing can
- * be planted.  Line-search state can be planted at two points, per instance, a NaN leaving the field as the product made it:
- *   plant0 [B][22] (or NULL), before the evaluation launches, together with the rows: f0, th0, ls0 (objective, infeasibility and
- *     sum log t of the overwritten rows -- the product takes them from the last accepted trial), the iteration counter, filt_mu,
- *     nfilt, filt_th[8], filt_phi[8].  The line-search start then forms phi0 and applies its own rules to them (theta_max /
- *     theta_min at iteration 0, filter reset when mu != filt_mu);
- *   plant1 [B][19] (or NULL), after k_step: nfilt, filt_th[8], filt_phi[8], theta_max, theta_min.
- * Returned per instance: dzeta, dt, dz, state as from bmpc_debug_newton_step (taken before the trial launch); zeta0 [B][N-1][41]
- * and t0, z0 [B][N-1][208], the iterate the search started from; zeta1, t1, z1, the iterate after it (with given rows every slot of
- * the copies the trial writes holds a NaN beforehand: slots the search did not write stay NaN -- except that bmpc_k_trial_spec
- * copies whole candidate records over when the accepted trial is not the first, slots no row uses included; with t, z == NULL
- * inactive slots keep t = 1, z = 0; an instance that finished at entry: NaN); ls [B][36]: ap, ad (fraction-to-boundary lengths),
- * D (merit derivative), phi0, alpha (accepted step length; 1e300: all ten trials rejected, the tenth kept), bt (rejected trials),
- * f0, th0, ls0 of the new iterate, nfilt, filt_th[8], filt_phi[8] (NaN beyond nfilt), theta_max, theta_min, it, flip, hess_mode, state, mu, filt_mu,
- * 0, 0.  Host pointers; B <= workspace slots; hess = 2.  rc 1 on misuse. */
-int bmpc_debug_line_search(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                           const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
-                           double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                           double* zeta1, double* t1, double* z1, double* ls);
-/* Test entry: the sequence of bmpc_debug_line_search with the iteration-control state of every instance planted before the
- * evaluation launches and returned -- what decides whether there is another iteration and with which Hessian, barrier parameter
- * and delta_w (the KKT test, the barrier update and the factorisation attempts of the Riccati kernels; the Hessian choice at the end
- * of the line search).  tol, max_iter, hess_switch, inertia_err, stall_n, gn_backoff, mu_floor_k, dw0 are the handle's options.
- *   ctl_plant [B][8] (or NULL; a NaN leaves a field as the init launch and `mode` made it): mu, err_prev, err_best, stall, dw_last,
- *     gn_back, gn_skip, it (planted after plant0: its iteration counter wins);
- *   ctl [B][20]: after the direction launches state, status (-1: not finished), mu, delta_w, tries, ksel, hess_mode, err_prev,
- *     err_best, stall, dw_last, gn_back, gn_skip, it, fk; after the trial launch it, hess_mode, gn_skip, state; 0.
- * Everything else as bmpc_debug_line_search.  Host pointers; B <= workspace slots; hess = 2.  rc 1 on misuse. */
-int bmpc_debug_iteration_control(bmpc_handle* h, int B, const double* x0, const double* lbx, const double* ubx, const double* p,
-                                 const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
-                                 double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                                 double* zeta1, double* t1, double* z1, double* ls, const double* ctl_plant, double* ctl);
+/* Test entry: ONE super-step of the product's kernels for B instances at the points x0, from a planted state, stopped where the
+ * requested outputs say.  The sequence, every step in brackets only when its arrays are given:
+ *   the product's init launch -> [rows and mode overwritten] -> [plant0] -> [ctl_plant] -> the product's evaluation launches
+ *     -> (H: the stage matrices out, stop)
+ *     -> the product's Riccati launch in the variant B live instances select, k_fwd, k_step -> the Newton step out -> [ctl, first part]
+ *     -> (no trial outputs: stop) | [plant1] -> the product's trial launch once, in the variant the number of groups of pairs
+ *        selects (bmpc_k_trial_spec / bmpc_k_trial) -> the trial outputs -> [ctl, second part]
+ * No list rotation.  H is requested alone; otherwise dzeta, dt, dz, state are required, and the seven trial outputs come all or
+ * none.  When the trial runs, the handle's trial_repeats must be the default (>= 9): the whole search ends inside the launch.
+ * tol, max_iter, hess_switch, inertia_err, stall_n, gn_backoff, mu_floor_k, dw0 are the handle's options.  Host pointers, per
+ * instance [B][...]; B <= workspace slots; the handle must have been created with hess = 2.  rc 1 on misuse, before anything is
+ * launched.  A NaN in a planted record leaves the field as the product made it. */
+typedef struct bmpc_debug_step {
+    const double *x0, *lbx, *ubx, *p;   /* the problems, as for bmpc_solve (required) */
+    /* GIVEN row slacks / multipliers t, z [N-1][208] (row slots of csrc/bmpc_device.hpp) and mode: the Hessian of the first
+     * factorisation attempt -- 0 Gauss-Newton, 1 exact, 2 exact with the KKT error of the previous iterate set to 0 (a failed attempt is
+     * then answered by delta_w, not by the Gauss-Newton fallback).  All three, or all three NULL: the rows stay as the init launch made
+     * them (the merit pieces are then those of the init launch) and nothing can be planted.  With H the mode is not used: the
+     * matrices are those of the exact Hessian. */
+    const double *t, *z;
+    const int* mode;
+    /* plant0 [22] (or NULL), before the evaluation launches, together with the rows: f0, th0, ls0 (objective, infeasibility and
+     *   sum log t of the overwritten rows -- the product takes them from the last accepted trial), the iteration counter, filt_mu,
+     *   nfilt, filt_th[8], filt_phi[8].  The line-search start then forms phi0 and applies its own rules to them (theta_max /
+     *   theta_min at iteration 0, filter reset when mu != filt_mu).  With the trial outputs only;
+     * plant1 [19] (or NULL), after k_step: nfilt, filt_th[8], filt_phi[8], theta_max, theta_min.  With the trial outputs only;
+     * ctl_plant [8] (or NULL), the iteration-control state -- what decides whether there is another iteration and with which Hessian,
+     *   barrier parameter and delta_w (the KKT test, the barrier update and the factorisation attempts of the Riccati kernels; the
+     *   Hessian choice at the end of the line search): mu, err_prev, err_best, stall, dw_last, gn_back, gn_skip, it (planted after
+     *   plant0: its iteration counter wins; a NaN leaves what the init launch and `mode` made).  With the trial outputs only. */
+    const double *plant0, *plant1, *ctl_plant;
+    /* with H only: GIVEN adjoint multipliers of the pi dynamics [N][3] (stage k uses lam_pi[k+1]) */
+    const double* lam_pi;
+    /* the stage matrices the Riccati sweep factorises (zeta coordinates, [N-1][41][41], row-major): a kernel of the entry's own runs
+     * the sweep's load phase per stage and copies the matrix out.  Needs t, z and lam_pi. */
+    double* H;
+    /* the Newton step: dzeta [N-1][41]; the row steps dt, dz [N-1][208] (NaN in the slots k_step did not write: padding slots are left
+     * untouched); state [12] with the fields of bmpc_debug_inst_state, where state[1] is -1 when the instance took a step and its
+     * final status (0 converged at entry, 3 every factorisation attempt failed) otherwise, [2] the barrier parameter the forward start
+     * used, [4] / [5] the dual / primal fraction-to-boundary lengths, [6] delta_w, [7] the mode the FIRST attempt ran with, [8] the
+     * retries.  Taken before the trial launch. */
+    double *dzeta, *dt, *dz, *state;
+    /* the trial outputs: zeta0 [N-1][41] and t0, z0 [N-1][208], the iterate the search started from; zeta1, t1, z1, the iterate after it
+     * (with given rows every slot of the copies the trial writes holds a NaN beforehand: slots the search did not write stay NaN --
+     * except that bmpc_k_trial_spec copies whole candidate records over when the accepted trial is not the first, slots no row uses
+     * included; with t, z == NULL inactive slots keep t = 1, z = 0; an instance that finished at entry: NaN); ls [36]: ap, ad
+     * (fraction-to-boundary lengths), D (merit derivative), phi0, alpha (accepted step length; 1e300: all ten trials rejected, the
+     * tenth kept), bt (rejected trials), f0, th0, ls0 of the new iterate, nfilt, filt_th[8], filt_phi[8] (NaN beyond nfilt),
+     * theta_max, theta_min, it, flip, hess_mode, state, mu, filt_mu, 0, 0. */
+    double *zeta0, *t0, *z0, *zeta1, *t1, *z1, *ls;
+    /* ctl [20] (or NULL; with the trial outputs only): after the direction launches state, status (-1: not finished), mu, delta_w,
+     * tries, ksel, hess_mode, err_prev, err_best, stall, dw_last, gn_back, gn_skip, it, fk; after the trial launch it, hess_mode,
+     * gn_skip, state; 0. */
+    double* ctl;
+} bmpc_debug_step;
+int bmpc_debug_superstep(bmpc_handle* h, int B, const bmpc_debug_step* s);
 /* Test entry: ONE part of the set growth of bmpc_convex_sets per item, one GPU thread per item, the same device functions as the
  * product's kernel (tests/test_set_growth_gpu.py compares them with an exact projection and an optimality certificate).
  *   mode 0  one round of the polyhedron growth around p [B][3] in a GIVEN metric E [B][9] (symmetric positive definite; the product's

@@ -26,6 +26,7 @@ static thread_local int t_lane = 0;
 #include "../../boundplanner_amd/csrc/bmpc_ric_kernel.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_stage_matrix.hpp"
 #include "../../boundplanner_amd/csrc/bmpc_robot.hpp"
+#include "../../boundplanner_amd/csrc/bmpc_debug_step.hpp"      // (and with it include/boundmpc.h: the record of emu_superstep)
 
 using namespace bmpc;
 #ifndef EMU_TRIAL_NW
@@ -51,12 +52,12 @@ template <class F> static void launch(int nblocks, F body, int nt = 64) {
 }
 
 static bool env_on(const char* name) { const char* e = getenv(name); return e && atoi(e); }      // read at call time: the tests set the knobs with monkeypatch
-// bmpc_default_opts, for the two test entries
+// bmpc_default_opts, for emu_superstep
 static SolverOpts default_opts(int N, double dt) { return SolverOpts{N, dt, 1e-5, 100, 2, 1.0, 0.1, 0.1, 2.0, 1000.0, 1e4, 1e-4, 1e-2, 0.0, 2, 8, 2, 1, 9}; }
 
 // Everything a run of the kernel bodies needs beside the caller's arrays -- workspace, instance state, lists, counters, scatter table,
 // LDS buffer -- with a PipeArgs wired to it, and the launch sequences of bmpc_pipeline.hip (bmpc_pipe_launch_init, launch_eval,
-// launch_direction) as members.  A points into the rig: it is neither copied nor moved.
+// launch_direction, launch_trial, bmpc_pipe_launch_superstep) as members.  A points into the rig: it is neither copied nor moved.
 struct Rig {
     const int N, cap;           // pool of `cap` slots
     const int nb_inst, nw;      // grids over all slots: threads per instance / groups of pairs
@@ -102,9 +103,9 @@ struct Rig {
         k_pool_reset_body(A, false);
     }
     // (the test entries) rows, and with `mode` the first attempt's Hessian mode, written over the initial ones
-    size_t nset() const { return (size_t)A.B * (N - 1) * NSLOT; }
+    int nb_slot() const { return (int)(((size_t)A.B * (N - 1) * NSLOT + 63) / 64); }      // grid of one thread per (instance, stage, slot)
     void set_rows(const double* t, const double* z, const int* mode = nullptr) {
-        launch((int)((nset() + 63) / 64), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z, mode); });
+        launch(nb_slot(), [&](int blk, int l) { k_set_rows_body(A, (size_t)blk * 64 + l, t, z, mode); });
     }
     // launch_eval for n groups of pairs: k_points, k_pose, k_eval (split: the two-wavefront pair of the tail regime on the GPU), then
     // k_curv for the curvature list -- which must have n_curv entries if that is given (false, k_curv not run, otherwise)
@@ -136,6 +137,30 @@ struct Rig {
     void trial(bool spec) {
         if (spec) launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_spec_body(A, blk, l, lds.data()); }, 64 * TRIAL_SPEC);
         else launch(waves_for(N, cnt[2]), [&](int blk, int l) { k_trial_body_t<EMU_TRIAL_NW>(A, blk, l, lds.data()); }, 64 * EMU_TRIAL_NW);
+    }
+    // bmpc_pipe_launch_superstep, launch by launch in its order (d: the record of bmpc_debug_superstep, checked by the caller), with
+    // the variants the GPU selects by batch size given as switches.  false: the stage-matrix path found an instance missing from the
+    // curvature list.
+    bool superstep(const bmpc_debug_step* d, bool eval_split, bool ric_spec, bool trial_spec) {
+        const int nbi = (A.B + 63) / 64, nb = nb_slot();      // grids of one thread per instance / per (instance, stage, slot)
+        const bool search = d->ls != nullptr;
+        if (d->t) set_rows(d->t, d->z, d->H ? nullptr : d->mode);
+        if (search && (d->t || d->plant0)) launch(nb, [&](int blk, int l) { k_ls_plant_body(A, (size_t)blk * 64 + l, d->plant0, 0, d->t ? 1 : 0); });
+        if (d->ctl_plant) launch(nbi, [&](int blk, int l) { k_ctl_plant_body(A, (size_t)blk * 64 + l, d->ctl_plant); });
+        if (!eval(nw, eval_split, d->H ? A.B : -1)) return false;
+        if (d->H) {
+            launch(A.B, [&](int b, int l) { k_stage_matrix_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&A), b, l, lds.data(), d->lam_pi, d->H); }, EMU_RIC_NT);
+            return true;
+        }
+        direction(ric_spec);
+        launch(nb, [&](int blk, int l) { k_newton_out_body(A, (size_t)blk * 64 + l, d->dzeta, d->dt, d->dz, d->state); });
+        if (d->ctl) launch(nbi, [&](int blk, int l) { k_ctl_out_body(A, (size_t)blk * 64 + l, d->ctl, 0); });
+        if (!search) return true;
+        if (d->plant1) launch(nb, [&](int blk, int l) { k_ls_plant_body(A, (size_t)blk * 64 + l, d->plant1, 1, 0); });
+        trial(trial_spec);
+        launch(nb, [&](int blk, int l) { k_ls_out_body(A, (size_t)blk * 64 + l, d->zeta0, d->t0, d->z0, d->zeta1, d->t1, d->z1, d->ls); });
+        if (d->ctl) launch(nbi, [&](int blk, int l) { k_ctl_out_body(A, (size_t)blk * 64 + l, d->ctl, 1); });
+        return true;
     }
 };
 
@@ -182,95 +207,23 @@ extern "C" int emu_pipe_solve(int N, double dt, double tol, int max_iter, int he
     return steps;
 }
 
-// The stage matrices the Riccati sweep factorises, at a GIVEN point with GIVEN row slacks / multipliers and adjoint multipliers of
-// the pi dynamics (tests/test_hessian_pin.py): the slots are initialised by the k_init* bodies from x0 = w, then t, z
-// ([B][N-1][NSLOT], slot numbering of bmpc_device.hpp) and hess_mode = 1 are written over the initial ones; k_points, k_pose,
-// k_eval (split = 0: k_eval_body<0>; 1: the two-wavefront pair <2> + <1>) and k_curv run once; then ric_phase_load_impl<128> runs
-// per (instance, stage) with lam_pi[b][k + 1] in R_lam and the stage matrix it leaves in LDS (zeta coordinates) is copied to
-// H [B][N-1][41][41] (k_set_rows_body, k_stage_matrix_body: bmpc_stage_matrix.hpp, the bodies of bmpc_debug_stage_matrices).
-extern "C" int emu_stage_matrices(int N, double dt, int B, const double* w, const double* lbx, const double* ubx, const double* p,
-                                  const double* t, const double* z, const double* lam_pi, int split, double* H) {
-    Rig R(B, B, 1, default_opts(N, dt), w, lbx, ubx, p);
+// One super-step of the kernel bodies from a planted state (tests/test_hessian_pin.py, test_newton_step.py, test_line_search.py,
+// test_iteration_control.py): the sequence of bmpc_debug_superstep (include/boundmpc.h) on the same record, with the same argument
+// check.  The slots are initialised by the k_init* bodies from x0 with bmpc_default_opts, of which tol, max_iter, mu_floor_k and dw0
+// are given; the rest is Rig::superstep.  Variants: eval_split runs k_eval as the two-wavefront pair <2> + <1> instead of
+// k_eval_body<0>; ric_spec the speculative pair k_ric_att_body + k_ric_body<RESUME> with three attempts instead of k_ric_body (the
+// kernels bmpc_k_ric / bmpc_k_ric_lat); trial_spec k_trial_spec_body (bmpc_k_trial_spec) instead of k_trial_body (bmpc_k_trial).
+// The default trial_repeats: the search ends inside the trial body.  rc 1: the arguments; -1: the curvature list.
+struct emu_step_cfg {
+    int N, max_iter, eval_split, ric_spec, trial_spec;
+    double dt, tol, mu_floor_k, dw0;
+};
+extern "C" int emu_superstep(const emu_step_cfg* c, int B, const bmpc_debug_step* s) {
+    if (!c || bmpc_debug_step_refusal(B, s)) return 1;
+    SolverOpts o = default_opts(c->N, c->dt);
+    o.tol = c->tol; o.max_iter = c->max_iter; o.mu_floor_k = c->mu_floor_k; o.dw0 = c->dw0;
+    Rig R(B, B, 1, o, s->x0, s->lbx, s->ubx, s->p);
     R.own_outputs();
     R.init();
-    R.set_rows(t, z);
-    if (!R.eval(R.nw, split != 0, B)) return -1;            // every instance is in the curvature list
-    launch(B, [&](int b, int lane) {
-        k_stage_matrix_body<EMU_RIC_NT>(*reinterpret_cast<const PipeArgsH*>(&R.A), b, lane, R.lds.data(), lam_pi, H);
-    }, EMU_RIC_NT);
-    return 0;
-}
-
-// The Newton step of one super-step from a given state (tests/test_newton_step.py; the bodies of bmpc_debug_newton_step): slots
-// initialised by the k_init* bodies from x0 = w, rows and the first attempt's Hessian mode written over them (k_set_rows_body), then
-// k_points, k_pose, k_eval, k_curv, the Riccati body (variant 0: k_ric_body, the kernels bmpc_k_ric / bmpc_k_ric_lat; 1: the
-// speculative pair k_ric_att_body + k_ric_body<RESUME> with three attempts), k_fwd, k_step, and the copy-out k_newton_out_body.
-extern "C" int emu_newton_step(int N, double dt_, int B, const double* w, const double* lbx, const double* ubx, const double* p,
-                               const double* t, const double* z, const int* mode, int variant, double* dzeta, double* dt, double* dz,
-                               double* state) {
-    Rig R(B, B, 1, default_opts(N, dt_), w, lbx, ubx, p);
-    R.own_outputs();
-    R.init();
-    R.set_rows(t, z, mode);
-    R.eval(R.nw, false);
-    R.direction(variant == 1);
-    launch((int)((R.nset() + 63) / 64), [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
-    return 0;
-}
-
-// Newton step and filter line search of one super-step from a given state (tests/test_line_search.py; the bodies of
-// bmpc_debug_line_search): emu_newton_step's sequence -- rows and mode overwritten only when t is given --, line-search state planted
-// before the evaluation bodies (plant0, with a NaN in the copies the trial writes when rows are given) and after k_step (plant1)
-// (k_ls_plant_body; null = nothing), the copy-out of the Newton step, then the trial body ONCE (variant 0: k_trial_body, the kernel
-// bmpc_k_trial; 1: k_trial_spec_body, bmpc_k_trial_spec) with the default trial_repeats -- the search ends inside it --, no
-// k_rotate, and the copy-out k_ls_out_body.
-extern "C" int emu_line_search(int N, double dt_, int B, const double* w, const double* lbx, const double* ubx, const double* p,
-                               const double* t, const double* z, const int* mode, const double* plant0, const double* plant1,
-                               int variant, double* dzeta, double* dt, double* dz, double* state, double* zeta0, double* t0, double* z0,
-                               double* zeta1, double* t1, double* z1, double* ls) {
-    if ((t == nullptr) != (z == nullptr) || (t == nullptr) != (mode == nullptr) || (!t && (plant0 || plant1))) return 1;
-    Rig R(B, B, 1, default_opts(N, dt_), w, lbx, ubx, p);
-    R.own_outputs();
-    R.init();
-    const int nb = (int)((R.nset() + 63) / 64);
-    if (t) R.set_rows(t, z, mode);
-    if (t || plant0) launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant0, 0, t ? 1 : 0); });
-    R.eval(R.nw, false);
-    R.direction(false);
-    launch(nb, [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
-    if (plant1) launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant1, 1, 0); });
-    R.trial(variant == 1);
-    launch(nb, [&](int blk, int l) { k_ls_out_body(R.A, (size_t)blk * 64 + l, zeta0, t0, z0, zeta1, t1, z1, ls); });
-    return 0;
-}
-
-// The iteration control of one super-step from a given state (tests/test_iteration_control.py; the bodies of
-// bmpc_debug_iteration_control): emu_line_search's sequence with the given tol, max_iter, mu_floor_k and dw0, the iteration-control state planted
-// after the rows (k_ctl_plant_body; null = nothing) and copied out after k_step and after the trial body (k_ctl_out_body).
-// ric_variant 0: k_ric_body; 1: the speculative pair k_ric_att_body + k_ric_body<RESUME> with three attempts.  The trial body is
-// k_trial_spec_body.
-extern "C" int emu_iteration_control(int N, double dt_, double tol, int max_iter, double mu_floor_k, double dw0, int B, const double* w, const double* lbx, const double* ubx,
-                                     const double* p, const double* t, const double* z, const int* mode, const double* plant0,
-                                     const double* plant1, const double* ctl_plant, int ric_variant, double* dzeta, double* dt, double* dz,
-                                     double* state, double* zeta0, double* t0, double* z0, double* zeta1, double* t1, double* z1, double* ls,
-                                     double* ctl) {
-    if (!t || !z || !mode) return 1;
-    SolverOpts o = default_opts(N, dt_);
-    o.tol = tol; o.max_iter = max_iter; o.mu_floor_k = mu_floor_k; o.dw0 = dw0;
-    Rig R(B, B, 1, o, w, lbx, ubx, p);
-    R.own_outputs();
-    R.init();
-    const int nb = (int)((R.nset() + 63) / 64), nbi = (B + 63) / 64;
-    R.set_rows(t, z, mode);
-    launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant0, 0, 1); });
-    if (ctl_plant) launch(nbi, [&](int blk, int l) { k_ctl_plant_body(R.A, (size_t)blk * 64 + l, ctl_plant); });
-    R.eval(R.nw, false);
-    R.direction(ric_variant == 1);
-    launch(nb, [&](int blk, int l) { k_newton_out_body(R.A, (size_t)blk * 64 + l, dzeta, dt, dz, state); });
-    launch(nbi, [&](int blk, int l) { k_ctl_out_body(R.A, (size_t)blk * 64 + l, ctl, 0); });
-    if (plant1) launch(nb, [&](int blk, int l) { k_ls_plant_body(R.A, (size_t)blk * 64 + l, plant1, 1, 0); });
-    R.trial(true);
-    launch(nb, [&](int blk, int l) { k_ls_out_body(R.A, (size_t)blk * 64 + l, zeta0, t0, z0, zeta1, t1, z1, ls); });
-    launch(nbi, [&](int blk, int l) { k_ctl_out_body(R.A, (size_t)blk * 64 + l, ctl, 1); });
-    return 0;
+    return R.superstep(s, c->eval_split != 0, c->ric_spec != 0, c->trial_spec != 0) ? 0 : -1;
 }

@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 
 import emu_build
+from boundplanner_amd.solver import STOPS, BmpcDebugStep, debug_step      # (ctypes and numpy only: no GPU, no library)
 
 LIB = "libbmpc_emupipe.so"
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -44,88 +45,48 @@ def solve_batch(N, x0, lbx, ubx, p, dt=0.1, tol=1e-5, max_iter=100, hess=2, hess
     return dict(x=x, g=g, f=f, iters=it, status=st, viol=viol, steps=steps, lam_g=lam_g, lam_x=lam_x)
 
 
-def stage_matrices(N, w, lbx, ubx, p, t, z, lam_pi, dt=0.1, split=0):
-    """emu_stage_matrices: H [B][N-1][41][41] from the kernel bodies at the points w [B][n_w] with row (t, z) [B][N-1][208] in the
-    kernels' slot numbering and lam_pi [B][N][3]; split = 1 runs k_eval as the two-wavefront pair."""
+class EmuStepCfg(ctypes.Structure):
+    """emu_step_cfg of tests/emu/emu_pipe.cpp, with bmpc_default_opts' values of the four options."""
+    _fields_ = [(k, ctypes.c_int) for k in ("N", "max_iter", "eval_split", "ric_spec", "trial_spec")] + \
+               [(k, ctypes.c_double) for k in ("dt", "tol", "mu_floor_k", "dw0")]
+    DEFAULTS = dict(max_iter=100, dt=0.1, tol=1e-5, mu_floor_k=1e4, dw0=1e-4)
+
+
+def superstep(N, want, cfg, **arrays):
+    """emu_superstep: the sequence of bmpc_debug_superstep run by the kernel bodies, on the record solver.debug_step makes of the
+    named arrays; cfg: fields of EmuStepCfg other than the defaults.  The dict of the outputs `want` names."""
     lib = ctypes.CDLL(build())
-    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
-    B = w.shape[0]
-    t, z, lam_pi = (np.ascontiguousarray(a, float) for a in (t, z, lam_pi))
-    assert t.shape == z.shape == (B, N - 1, 208) and lam_pi.shape == (B, N, 3)
-    H = np.zeros((B, N - 1, 41, 41))
-    P = lambda a: a.ctypes.data_as(_dp)
-    rc = lib.emu_stage_matrices(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z), P(lam_pi), split, P(H))
+    lib.emu_superstep.argtypes = [ctypes.POINTER(EmuStepCfg), ctypes.c_int, ctypes.POINTER(BmpcDebugStep)]
+    B, step, out = debug_step(N, want, **arrays)
+    rc = lib.emu_superstep(ctypes.byref(EmuStepCfg(N=N, **{**EmuStepCfg.DEFAULTS, **cfg})), B, ctypes.byref(step))
     assert rc == 0, rc
-    return H
+    return out
+
+
+def stage_matrices(N, w, lbx, ubx, p, t, z, lam_pi, dt=0.1, split=0):
+    """H [B][N-1][41][41] from the kernel bodies at the points w [B][n_w] with row (t, z) [B][N-1][208] in the kernels' slot
+    numbering and lam_pi [B][N][3]; split = 1 runs k_eval as the two-wavefront pair."""
+    return superstep(N, STOPS["H"], dict(dt=dt, eval_split=split), x0=w, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=1, lam_pi=lam_pi)["H"]
 
 
 def newton_step(N, w, lbx, ubx, p, t, z, mode, dt=0.1, variant=0):
-    """emu_newton_step: (dzeta [B][N-1][41], dt [B][N-1][208], dz [B][N-1][208], state [B][12]) of one super-step of the kernel
-    bodies at the points w [B][n_w] with row (t, z) [B][N-1][208] and first-attempt Hessian mode [B]; variant = 1 runs the
-    speculative pair of Riccati bodies."""
-    lib = ctypes.CDLL(build())
-    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
-    B = w.shape[0]
-    t, z = (np.ascontiguousarray(a, float) for a in (t, z))
-    mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
-    assert t.shape == z.shape == (B, N - 1, 208)
-    dzeta, dts, dzs, state = np.zeros((B, N - 1, 41)), np.zeros((B, N - 1, 208)), np.zeros((B, N - 1, 208)), np.zeros((B, 12))
-    P = lambda a: a.ctypes.data_as(_dp)
-    rc = lib.emu_newton_step(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z), mode.ctypes.data_as(_ip), variant,
-                             P(dzeta), P(dts), P(dzs), P(state))
-    assert rc == 0, rc
-    return dzeta, dts, dzs, state
-
-
-LS_SHAPES = lambda B, N: dict(dzeta=(B, N - 1, 41), dt=(B, N - 1, 208), dz=(B, N - 1, 208), state=(B, 12), zeta0=(B, N - 1, 41),
-                              t0=(B, N - 1, 208), z0=(B, N - 1, 208), zeta1=(B, N - 1, 41), t1=(B, N - 1, 208), z1=(B, N - 1, 208), ls=(B, 36))
+    """(dzeta [B][N-1][41], dt [B][N-1][208], dz [B][N-1][208], state [B][12]) of one super-step of the kernel bodies at the points
+    w [B][n_w] with row (t, z) [B][N-1][208] and first-attempt Hessian mode [B]; variant = 1 runs the speculative pair of Riccati
+    bodies."""
+    return tuple(superstep(N, STOPS["newton"], dict(dt=dt, ric_spec=variant), x0=w, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=mode).values())
 
 
 def line_search(N, w, lbx, ubx, p, t=None, z=None, mode=None, plant0=None, plant1=None, dt=0.1, variant=1):
-    """emu_line_search: Newton step and filter line search of one super-step of the kernel bodies (the bodies of
-    bmpc_debug_line_search; same arguments and the same dict as HipBoundMPC.line_search); variant 1: k_trial_spec_body (what the
-    GPU runs for a small batch), 0: k_trial_body."""
-    lib = ctypes.CDLL(build())
-    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
-    B = w.shape[0]
-    P = lambda a: a.ctypes.data_as(_dp) if a is not None else None
-    if t is not None:
-        t, z = (np.ascontiguousarray(a, float) for a in (t, z))
-        mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
-        assert t.shape == z.shape == (B, N - 1, 208)
-    if plant0 is not None:
-        plant0 = np.ascontiguousarray(plant0, float); assert plant0.shape == (B, 22)
-    if plant1 is not None:
-        plant1 = np.ascontiguousarray(plant1, float); assert plant1.shape == (B, 19)
-    out = {k: np.zeros(v) for k, v in LS_SHAPES(B, N).items()}
-    rc = lib.emu_line_search(N, ctypes.c_double(dt), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z),
-                             mode.ctypes.data_as(_ip) if mode is not None else None, P(plant0), P(plant1), variant,
-                             *(P(out[k]) for k in out))
-    assert rc == 0, rc
-    return out
+    """Newton step and filter line search of one super-step of the kernel bodies (same arguments and the same dict as
+    HipBoundMPC.line_search); variant 1: k_trial_spec_body (what the GPU runs for a small batch), 0: k_trial_body."""
+    return superstep(N, STOPS["ls"], dict(dt=dt, trial_spec=variant), x0=w, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=mode, plant0=plant0,
+                     plant1=plant1)
 
 
 def iteration_control(N, w, lbx, ubx, p, t, z, mode, ctl_plant=None, plant0=None, plant1=None, dt=0.1, tol=1e-5, max_iter=100, mu_floor_k=1e4, dw0=1e-4, variant=0):
-    """emu_iteration_control: the bodies of bmpc_debug_iteration_control (same arguments and the same dict as
-    HipBoundMPC.iteration_control, tol, max_iter, mu_floor_k and dw0 being the handle's there); variant 1 runs the speculative pair of Riccati bodies."""
-    lib = ctypes.CDLL(build())
-    lbx = np.where(np.isinf(lbx), -1e20, lbx); ubx = np.where(np.isinf(ubx), 1e20, ubx)
-    w, lbx, ubx, p = (np.ascontiguousarray(np.atleast_2d(a), float) for a in (w, lbx, ubx, p))
-    B = w.shape[0]
-    P = lambda a: a.ctypes.data_as(_dp) if a is not None else None
-    t, z = (np.ascontiguousarray(a, float) for a in (t, z))
-    mode = np.ascontiguousarray(np.broadcast_to(mode, (B,)), np.int32)
-    assert t.shape == z.shape == (B, N - 1, 208)
-    plant0, plant1, ctl_plant = (None if a is None else np.ascontiguousarray(a, float) for a in (plant0, plant1, ctl_plant))
-    assert plant0 is None or plant0.shape == (B, 22)
-    assert plant1 is None or plant1.shape == (B, 19)
-    assert ctl_plant is None or ctl_plant.shape == (B, 8)
-    out = {k: np.zeros(v) for k, v in LS_SHAPES(B, N).items()}
-    out["ctl"] = np.zeros((B, 20))
-    rc = lib.emu_iteration_control(N, ctypes.c_double(dt), ctypes.c_double(tol), int(max_iter), ctypes.c_double(mu_floor_k), ctypes.c_double(dw0), B, P(w), P(lbx), P(ubx), P(p), P(t), P(z),
-                                   mode.ctypes.data_as(_ip), P(plant0), P(plant1), P(ctl_plant), variant, *(P(out[k]) for k in out))
-    assert rc == 0, rc
-    return out
+    """The same with the iteration-control state planted and returned (same arguments and the same dict as
+    HipBoundMPC.iteration_control, tol, max_iter, mu_floor_k and dw0 being the handle's there); variant 1 runs the speculative pair
+    of Riccati bodies.  The trial body is k_trial_spec_body."""
+    cfg = dict(dt=dt, tol=tol, max_iter=int(max_iter), mu_floor_k=mu_floor_k, dw0=dw0, ric_spec=variant, trial_spec=1)
+    return superstep(N, STOPS["ctl"], cfg, x0=w, lbx=lbx, ubx=ubx, p=p, t=t, z=z, mode=mode, plant0=plant0, plant1=plant1,
+                     ctl_plant=ctl_plant)

@@ -1,7 +1,7 @@
 """The Newton step of the HIP kernels, pinned to a dense KKT solve (MI355X; tests/test_newton_step.py is the CPU half and documents
 the checks, the profiles, the bounds and the figures they come from).
 
-bmpc_debug_newton_step: slots initialised by the product's init launch, rows and the first attempt's Hessian mode overwritten, the
+bmpc_debug_superstep stopped after the direction launches: slots initialised by the product's init launch, rows and the first attempt's Hessian mode overwritten, the
 product's evaluation launches, the product's own Riccati launch in the variant the number of live instances selects, bmpc_k_fwd,
 bmpc_k_step, and a copy-out kernel.  The cases of newton_step_lib.CASES run below BMPC_RIC_SPEC_BELOW / BMPC_RIC_LAT_BELOW
 (bmpc_k_ric_att + bmpc_k_ric_sel); one more batch at N = 6 has as many instances as the larger of the two thresholds, so that the
@@ -114,3 +114,36 @@ def test_entries_of_different_kinds_leave_nothing_behind_on_a_handle():
     assert same_solve(s1, solve(_handle(N))), "solve differs from a fresh handle's"
     assert same(n1, _run(_handle(N), bt)), "newton_step after a solve differs from a fresh handle's first call"
     assert np.array_equal(m1, stage(_handle(N))), "stage_matrices after a solve and a newton_step differs from a fresh handle's first call"
+
+
+def test_a_misused_entry_is_refused_and_leaves_nothing_behind():
+    """bmpc_debug_superstep checks its record on the host before anything is launched (include/boundmpc.h).  N = 4, B = 2: every
+    misuse raises with rc 1, and the newton_step that follows on the same handle has the bit patterns of a fresh handle's.  A
+    handle whose line search does not end inside one launch (trial_repeats = 1) is refused the line search and served the Newton
+    step."""
+    from boundplanner_amd.solver import STOPS, HipBoundMPC
+    N, B = 4, 2
+    bt = NS.make_batch(N, B, 11, "a")
+    lam_pi = np.random.default_rng(12).normal(size=(B, N, 3))
+    prob = dict(x0=bt["x0"], lbx=bt["lbx"], ubx=bt["ubx"], p=bt["p"])
+    rows = dict(prob, t=bt["TS"], z=bt["ZS"], mode=bt["mode"])
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint64)
+    same = lambda a, b: all(u.shape == v.shape and np.array_equal(bits(u), bits(v)) for u, v in zip(a, b))
+    fresh = _run(_handle(N), bt)
+    h = _handle(N)
+    misuses = {
+        "t without z": (STOPS["newton"], dict(prob, t=bt["TS"], mode=bt["mode"])),
+        "a plant without rows": (STOPS["ls"], dict(prob, plant0=np.full((B, 22), np.nan))),
+        "mode = 3": (STOPS["newton"], dict(rows, mode=3)),
+        "H together with the ls group": (STOPS["H"] + STOPS["ls"], dict(rows, lam_pi=lam_pi)),
+        "H without lam_pi": (STOPS["H"], rows),
+        "ctl without the ls group": (STOPS["newton"] + ("ctl",), rows),
+    }
+    for what, (want, arrays) in misuses.items():
+        with pytest.raises(RuntimeError, match=r"\(1\)"):
+            h._superstep(want, **arrays)
+        assert same(fresh, _run(h, bt)), f"newton_step after the refusal of {what} differs from a fresh handle's"
+    short = HipBoundMPC(N, trial_repeats=1)
+    with pytest.raises(RuntimeError, match=r"\(1\).*trial_repeats"):
+        short.line_search(*(rows[k] for k in ("x0", "lbx", "ubx", "p", "t", "z", "mode")))
+    assert same(fresh, _run(short, bt)), "newton_step of a handle with trial_repeats = 1 differs from the default handle's"
